@@ -19,6 +19,12 @@ needs (5.3 MiB each) use 5 GB of the 288 GB HBM.
 Multi-GPU: one process per GPU (torchrun), data-parallel engine replicas (weak scaling: each GPU
 serves its own batch of queries); ``--tp N`` runs tensor-parallel decode over RCCL instead.
 Weights are random-init (seeded) GPT-2-124M and prompts are synthetic token ids: no network.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.  ``--full``
+adds the unloaded p50 latency points (``--latency-batches``, keys ``p50_query_latency_ms_b<B>``),
+which take generations of their own after the timed steps; ``DLMS_BENCH_FULL=1`` in the environment
+is the same switch, for scripts that wrap the benchmark.  ``--dump-outputs DIR`` writes the
+token sequences the last timed step returned as ``DIR/*.npy`` (same arguments, same inputs).
 """
 from __future__ import annotations
 
@@ -118,6 +124,24 @@ def latency_point(eng, cfg, B: int, prompt_len: int, max_length: int, reps: int,
             f"prefill_ms_b{B}": round(st.prefill_ms / reps, 3)}
 
 
+def dump_outputs(out_dir: str, seqs: list[list[int]], max_length: int, rank: int) -> None:
+    """What a caller of the timed ``generate()`` received in the last timed step, as float32 .npy
+    files (token ids are < 2^24, so exact): ``tokens`` is one row per query, prompt + generated
+    ids, padded with -1 up to ``max_length``; ``lengths`` is each row's token count.  Rank 0
+    writes ``tokens.npy`` / ``lengths.npy``, rank r > 0 ``tokens_rank<r>.npy`` / ``lengths_rank<r>.npy``
+    (1024 queries x 150 tokens: 0.6 MB per rank)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tokens = np.full((len(seqs), max_length), -1.0, dtype=np.float32)
+    for i, row in enumerate(seqs):
+        tokens[i, : len(row)] = row
+    lengths = np.asarray([len(row) for row in seqs], dtype=np.float32)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(out_dir, f"tokens{tag}.npy"), tokens)
+    np.save(os.path.join(out_dir, f"lengths{tag}.npy"), lengths)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -133,7 +157,14 @@ def main():
     ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="fp8 = W8A8 e4m3 QKV/c_fc/LM head (not the headline: reduced precision)")
     ap.add_argument("--latency-batches", default="1,32",
-                    help="after the timed headline: unloaded p50 latency at these batch sizes ('' = skip)")
+                    help="with --full, after the timed headline: unloaded p50 latency at these batch sizes ('' = skip)")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("DLMS_BENCH_FULL", "0") not in ("", "0"),
+                    help="also measure what the headline does not need (the unloaded latency points of "
+                         "--latency-batches); a plain run only sets up, warms up and times --steps steps.  "
+                         "DLMS_BENCH_FULL=1 in the environment switches it on as well (for wrapper scripts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the token sequences of "
+                         "every query) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -196,9 +227,10 @@ def main():
     per_step_ms: list[float] = []
     stats = GenerateStats()
     t0 = time.perf_counter()
+    last_out: list[list[int]] = []
     for _ in range(args.steps):
         ts = time.perf_counter()
-        eng.generate(prompts, args.max_length, stats=stats)
+        last_out = eng.generate(prompts, args.max_length, stats=stats)
         if gpu:
             torch.cuda.synchronize()
         per_step_ms.append((time.perf_counter() - ts) * 1e3)
@@ -220,8 +252,10 @@ def main():
 
     tok_s = total_new / elapsed_max
     p50 = statistics.median(per_step_ms)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, last_out, args.max_length, rank)
     extra = {}
-    for lb in [int(b) for b in args.latency_batches.split(",") if b.strip()]:
+    for lb in [int(b) for b in args.latency_batches.split(",") if b.strip()] if args.full else []:
         if lb <= B:  # outside the timed region: the unloaded latency operating points
             extra.update(latency_point(eng, cfg, lb, args.prompt_len, args.max_length, 5, 2000 + dp_rank, gpu))
     if dist is not None:

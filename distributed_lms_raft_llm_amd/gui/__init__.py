@@ -2,7 +2,8 @@
 
 The reference ships a Tk client, ``lms_gui_final.py`` (components C15-C19:
 connection/leader discovery, login/register, student and instructor workflows, logout); it keeps
-working unchanged against this framework (``tests/test_gui_compat.py``).  This is the framework's
+working unchanged against this framework (verified by a test that needed a checkout of the
+reference project and is no longer in the suite).  This is the framework's
 own front end for the same workflows, designed around two defects of that client:
 
 * every RPC runs on a worker thread and its result is handed back to the Tk thread with

@@ -31,6 +31,8 @@
 #   sweep32:<...>    the same at batch 16 and 32                   -> gpurun_out/sweep1.jsonl
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
+# bench / benchng read the b1/b32 keys; every other bench.py call here passes --latency-batches ""
+export DLMS_BENCH_FULL=1  # bench.py --full: the result lines carry the unloaded latency keys (p50_query_latency_ms_b<B> ...)
 T="python -u -m pytest -x -q --timeout 180 --timeout-method thread"
 
 step() {  # step <seconds> <log> <cmd...>: own time limit; a fault, abort or timeout ends the call

@@ -1,4 +1,5 @@
 #!/bin/bash
+export DLMS_BENCH_FULL=1  # bench.py --full: the result lines carry the unloaded latency keys (p50_query_latency_ms_b<B> ...)
 # batch-1 prefill probe after a 1024-query run (bench.py order), A/B against launch-per-op and a short bench line
 #   gpurun -- bash scripts/prefill_probe.sh   -> gpurun_out/prefill_probe.jsonl, gpurun_out/bench_probe.log
 cd "$GRAFT_REPO_ROOT" || exit 1

@@ -80,13 +80,52 @@ def test_bench_rejects_mismatched_world_size():
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
 
 
-def test_bench_reports_latency_points():
-    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
-    p = subprocess.run([sys.executable, "bench.py", *ARGS, "--latency-batches", "1"], cwd=ROOT, env=env,
+def _latency_points(extra_args, extra_env):
+    env = {**os.environ, "CUDA_VISIBLE_DEVICES": "", "HIP_VISIBLE_DEVICES": "", "DLMS_BENCH_FULL": "0", **extra_env}
+    p = subprocess.run([sys.executable, "bench.py", *ARGS, *extra_args, "--latency-batches", "1"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
-    d = _json_lines(p.stdout)[0]
+    return _json_lines(p.stdout)[0]
+
+
+def test_bench_reports_latency_points():
+    d = _latency_points(["--full"], {})
     assert d["p50_query_latency_ms_b1"] > 0 and d["tok_s_b1"] > 0
+
+
+def test_bench_full_from_the_environment():
+    """``DLMS_BENCH_FULL=1`` (what the wrapper scripts export) is the same switch as ``--full``."""
+    d = _latency_points([], {"DLMS_BENCH_FULL": "1"})
+    assert d["p50_query_latency_ms_b1"] > 0 and d["tok_s_b1"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` the latency points are not measured; ``--dump-outputs`` writes the last
+    timed step's token sequences as float32 arrays: every row starts with its seeded prompt, and the
+    arrays are identical from run to run."""
+    import numpy as np
+    import torch
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", DLMS_BENCH_FULL="0")
+    dumps = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, "bench.py", *ARGS, "--dump-outputs", str(tmp_path / name)], cwd=ROOT,
+                           env=env, capture_output=True, text=True, timeout=240)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = _json_lines(p.stdout)[0]
+        assert KEYS <= set(d) and d["steps"] == 2 and d["ms_per_step"] > 0
+        assert not [k for k in d if k.startswith(("p50_query_latency_ms_b", "tok_s_b", "prefill_ms_b"))], d
+        assert sorted(os.listdir(tmp_path / name)) == ["lengths.npy", "tokens.npy"]
+        dumps.append((np.load(tmp_path / name / "tokens.npy"), np.load(tmp_path / name / "lengths.npy")))
+    tokens, lengths = dumps[0]
+    assert tokens.dtype == np.float32 and tokens.shape == (2, 24) and lengths.dtype == np.float32
+    assert lengths.tolist() == [24.0, 24.0] and (tokens >= 0).all() and (tokens == np.floor(tokens)).all()
+    # the rows are this run's queries: rank 0's prompts (seed 1000, ids below GPT-2's vocabulary of
+    # 50257) followed by 16 generated ids each
+    prompts = torch.randint(0, 50257 - 1, (2, 8), generator=torch.Generator().manual_seed(1000))
+    assert np.array_equal(tokens[:, :8], prompts.numpy().astype(np.float32))
+    assert (tokens[:, 8:] < 50257).all()
+    assert np.array_equal(tokens, dumps[1][0]) and np.array_equal(lengths, dumps[1][1])
 
 
 def test_bench_labels_are_model_correct():
