@@ -26,6 +26,7 @@
 //                   latency-bound skinny GEMMs put enough workgroups on the 256 CUs.
 #include "common.h"
 #include <atomic>
+#include <type_traits>
 #include <stdlib.h>
 
 enum { EPI_BF16 = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_F32 = 3, EPI_QKV = 4, EPI_ARGMAX = 5, EPI_PARTIAL = 6 };
@@ -38,6 +39,22 @@ enum { IN_BF16 = 0, IN_FP8 = 1 };
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glob_void_t;
+
+// Fragment reads as bare instructions with hand-counted waits.  The compiler books every LDS-DMA
+// as a flat access that may be pending on the LGKM counter too, and while one is in flight (here:
+// always) it turns each wait it inserts for a ds_read into lgkmcnt(0); the hardware counts the DMA
+// on vmcnt alone.  A value read this way may be used only behind a wait_lgkmcnt that covers it,
+// named in an empty asm ("+v") behind that wait so that no use can move above it.
+typedef __attribute__((address_space(3))) char lds_char_t;
+__device__ __forceinline__ bf16x8_t lds_read_b128_nowait(unsigned addr, int offset) {
+    bf16x8_t v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(offset) : "memory");
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void wait_lgkmcnt() {
+    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -53,6 +70,14 @@ __device__ __forceinline__ void wait_vmcnt() {
 // Synchronisation: counted `s_waitcnt vmcnt` + raw s_barrier (a __syncthreads() would drain the
 // in-flight DMA every step); out-of-range A rows read a clamped valid row (their results are never
 // stored), so the DMA never needs predication.
+// A bf16 step issues all its fragment reads at once (both 32-deep halves, 2 * (TM + TN) ds_read_b128)
+// and waits by count: lgkmcnt(TM + TN) before the first half's MFMAs, so the second half's fragments
+// land under them, lgkmcnt(0) before the second half's.  Each accumulator still sums k in ascending
+// order.  The reads are bare instructions with hand-placed waits (lds_read_b128_nowait below) because
+// the compiler's own waits degrade to lgkmcnt(0) while an LDS-DMA is in flight.
+// Prologue: the tile map (tiles, K slice, reciprocals for the two divisions) comes from the host in
+// GemmGeo, next to A / W / lda / ldw at the head of the kernel arguments: one group of scalar loads,
+// no runtime division, then the first STAGES-1 steps' DMA; accumulators and fragment offsets follow.
 //
 // MODE (big prefill GEMMs, 256x256 tiles; see launch_gemm_epi):
 //   bit 0  REGPF: a whole K-tile's fragments go LDS -> registers right after its barrier, so its
@@ -104,10 +129,45 @@ __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int
     }
 }
 
+// Launch geometry, computed once on the host (launch_gemm_cfg) so that the kernel's prologue holds no
+// runtime division: the workgroup -> (split, tile_n, tile_m) map divides by `tiles` and `tiles_m`
+// through multiply-high reciprocals.  With A, W, lda and ldw in front of it, everything the first
+// DMA's addresses need sits in the first 64 B of the kernel arguments.
+struct GemmGeo {
+    int M;
+    int nwg;                    // grid size = tiles * split_k (< 2^30)
+    int tiles;                  // output tiles (workgroups per K slice)
+    int tiles_m;                // row tiles
+    unsigned sp_mul, sp_shift;  // n / tiles
+    unsigned tm_mul, tm_shift;  // n / tiles_m
+    int k_len;                  // k-elements per K slice
+    int nk;                     // ring steps per K slice
+};
+
+// n / d = 2n / 2d for n < 2^30, d >= 1 as (2n * mul) >> (32 + shift).  With l = ceil(log2 2d) >= 1
+// and mul = floor(2^(31+l) / 2d) + 1 < 2^32: mul * 2d = 2^(31+l) + e with 0 < e <= 2d <= 2^l, so
+// 2n * mul / 2^(31+l) = n / d + 2n * e / (2d * 2^(31+l)), whose excess over n / d stays below
+// 1 / 2d for 2n < 2^31: the floor is exact.  (Dividing 2n by 2d keeps d = 1 on the same path.)
+static void magic_div_setup(unsigned d, unsigned* mul, unsigned* shift) {
+    const unsigned d2 = 2 * d;
+    const unsigned l = 32 - __builtin_clz(d2 - 1);
+    *mul = (unsigned)((1ull << (31 + l)) / d2 + 1);
+    *shift = l - 1;
+}
+__device__ __forceinline__ int magic_div(int n, unsigned mul, unsigned shift) {
+    return (int)(__umulhi((unsigned)n << 1, mul) >> shift);
+}
+// xcd_remap (common.h) without its branch and signed divisions: the first nwg % 8 XCDs own one
+// workgroup more, so XCD x's chunk starts at x * (nwg / 8) + min(x, nwg % 8)
+__device__ __forceinline__ int xcd_remap_u(unsigned orig, unsigned nwg) {
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+    return (int)(xcd * q + (xcd < r ? xcd : r) + (orig >> 3));
+}
+
 template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __restrict__ A, int lda,
-                                                      const void* __restrict__ W, int ldw, int M, int N,
-                                                      int K, GemmEpi ep) {
+__global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __restrict__ A,
+                                                      const void* __restrict__ W, int lda, int ldw,
+                                                      GemmGeo geo, int N, GemmEpi ep) {
     constexpr int EB = IN == IN_FP8 ? 1 : 2;    // bytes per element
     constexpr int BKE = GEMM_BK * 2 / EB;       // k-elements per ring step
     constexpr int NW = WM * WN;  // waves per workgroup (4 or 8)
@@ -130,16 +190,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    const int wm = wave / WN;
-    const int wn = wave % WN;
 
-    const int tiles_m = (M + BM - 1) / BM;
-    const int nwg = gridDim.x;
-    const int nsplit = EPI == EPI_PARTIAL ? ep.split_k : 1;
-    const int tiles = nwg / nsplit;
-    const int bid0 = xcd_remap(blockIdx.x, nwg);
-    const int split = bid0 / tiles;
-    const int bid = bid0 - split * tiles;
+    // workgroup -> (K slice, tile): scalar work on the one group of kernel-argument loads
+    const int M = geo.M;
+    const int tiles_m = geo.tiles_m;
+    const int bid0 = xcd_remap_u(blockIdx.x, (unsigned)geo.nwg);
+    const int split = EPI == EPI_PARTIAL ? magic_div(bid0, geo.sp_mul, geo.sp_shift) : 0;
+    const int bid = bid0 - split * geo.tiles;
     constexpr bool REGPF = (MODE & MODE_REGPF) != 0;
     constexpr bool GROUPED = (MODE & MODE_GROUPED) != 0;
     static_assert(!REGPF || (STAGES == 2 && IN == IN_BF16), "REGPF: 2 bf16 stages");
@@ -153,13 +210,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
         tile_m = gm0 + r % gsz;
         tile_n = r / gsz;
     } else {
-        tile_m = bid % tiles_m;
-        tile_n = bid / tiles_m;
+        tile_n = magic_div(bid, geo.tm_mul, geo.tm_shift);
+        tile_m = bid - tile_n * tiles_m;
     }
     const int m0 = tile_m * BM;
     const int n0 = tile_n * BN;
-    const int k_len = K / nsplit;
-    const int k_base = split * k_len;
+    const int k_base = split * geo.k_len;
+    const int nk = geo.nk;
 
     // per-lane DMA sources (fixed for the K loop; byte addresses)
     const char* src[PPW];
@@ -182,14 +239,23 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
             __builtin_amdgcn_global_load_lds((glob_void_t*)(src[i] + (size_t)k0 * EB),
                                              (lds_void_t*)(dst + (wave + NW * i) * 1024), 16, 0, 0);
     };
+    // ring prologue, ahead of everything the loads do not need (accumulators, fragment offsets,
+    // epilogue fields): up to STAGES-1 steps in flight; no step is ever loaded twice (short split-K
+    // slices would otherwise multiply their traffic)
+    if constexpr (!REGPF) {
+#pragma unroll
+        for (int s = 0; s < STAGES - 1; ++s)
+            if (s < nk) issue(s, s * BKE);
+    }
 
+    const int wm = wave / WN;
+    const int wn = wave % WN;
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-    const int nk = k_len / BKE;
     const int frow = lane & 15;
     const int fk = lane >> 4;
     const int fsw = lane & 7;  // == row & 7 for every fragment row this lane reads
@@ -232,14 +298,41 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
         }
     }
-    // prologue: up to STAGES-1 steps in flight; no step is ever loaded twice (short split-K slices
-    // would otherwise multiply their traffic)
-    if constexpr (!REGPF) {
+    // bf16 fragments of one whole K-step (both 32-deep halves), 2 * (TM + TN) ds_read_b128, issued
+    // without waiting: each is valid only behind frags_wait()
+    const unsigned lds_a = (unsigned)(size_t)(lds_char_t*)smem + (wm * WTM + frow) * ROWB;
+    const unsigned lds_w = (unsigned)(size_t)(lds_char_t*)smem + A_BYTES + (wn * WTN + frow) * ROWB;
+    const unsigned coff0 = (fk ^ fsw) << 4, coff1 = ((4 + fk) ^ fsw) << 4;
+    auto read_frags = [&](int stage, bf16x8_t (&af)[2][TM], bf16x8_t (&bfr)[2][TN]) {
 #pragma unroll
-        for (int s = 0; s < STAGES - 1; ++s)
-            if (s < nk) issue(s, s * BKE);
-    }
-
+        for (int ks = 0; ks < 2; ++ks) {
+            const unsigned aa = lds_a + stage * STAGE_BYTES + (ks ? coff1 : coff0);
+            const unsigned wa = lds_w + stage * STAGE_BYTES + (ks ? coff1 : coff0);
+#pragma unroll
+            for (int i = 0; i < TM; ++i) af[ks][i] = lds_read_b128_nowait(aa, i * 16 * ROWB);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bfr[ks][j] = lds_read_b128_nowait(wa, j * 16 * ROWB);
+        }
+    };
+    // s_waitcnt lgkmcnt(PENDING), then half ks of the fragments may be used
+    auto frags_wait = [&](auto pending, int ks, bf16x8_t (&af)[2][TM], bf16x8_t (&bfr)[2][TN]) {
+        __builtin_amdgcn_sched_barrier(0);  // (register-only MFMAs would otherwise sink below the wait)
+        wait_lgkmcnt<decltype(pending)::value>();
+#pragma unroll
+        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[ks][i]));
+#pragma unroll
+        for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bfr[ks][j]));
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mma = [&](int ks, const bf16x8_t (&af)[2][TM], const bf16x8_t (&bfr)[2][TN]) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+    };
+    using cnt0 = std::integral_constant<int, 0>;
+    using cnt_half = std::integral_constant<int, TM + TN>;
     for (int kt = 0; kt < (REGPF ? 0 : nk); ++kt) {
         // this lane's share of step kt has landed (steady state: STAGES-2 younger steps may stay in
         // flight; in the tail fewer were issued, so drain everything) ...
@@ -253,12 +346,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
             const int kn = kt + STAGES - 1;
             if (kn < nk) issue(kn % STAGES, kn * BKE);
         }
-        const char* as = smem + (kt % STAGES) * STAGE_BYTES + (wm * WTM) * ROWB;
-        const char* ws = smem + (kt % STAGES) * STAGE_BYTES + A_BYTES + (wn * WTN) * ROWB;
+        if constexpr (IN == IN_FP8) {
+            const char* as = smem + (kt % STAGES) * STAGE_BYTES + (wm * WTM) * ROWB;
+            const char* ws = smem + (kt % STAGES) * STAGE_BYTES + A_BYTES + (wn * WTN) * ROWB;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int coff = (((ks * 4 + fk) ^ fsw) << 4);
-            if constexpr (IN == IN_FP8) {
+            for (int ks = 0; ks < 2; ++ks) {
+                const int coff = (((ks * 4 + fk) ^ fsw) << 4);
                 // a 16-B chunk = 16 k-elements: bytes 0-7 feed one fp8 MFMA, bytes 8-15 the next.
                 // A and W use the same k permutation, so the dot products are unchanged.
                 long af[TM][2], bfr[TN][2];
@@ -282,22 +375,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
                         for (int j = 0; j < TN; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(af[i][h], bfr[j][h], acc[i][j],
                                                                                    0, 0, 0);
-            } else {
-                bf16x8_t af[TM], bfr[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-                    af[i] = *reinterpret_cast<const bf16x8_t*>(as + (i * 16 + frow) * ROWB + coff);
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    bfr[j] = *reinterpret_cast<const bf16x8_t*>(ws + (j * 16 + frow) * ROWB + coff);
-                // (s_setprio(1)/(0) around this cluster, cdna guide T5, measured null on this 1-barrier
-                // loop: prefill shapes and the whole decode within noise)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
             }
+        } else {
+            // (s_setprio(1)/(0) around the MFMA cluster, cdna guide T5, measured null on this 1-barrier
+            // loop: prefill shapes and the whole decode within noise)
+            bf16x8_t af[2][TM], bfr[2][TN];
+            read_frags(kt % STAGES, af, bfr);
+            frags_wait(cnt_half{}, 0, af, bfr);  // the second half's reads land under these MFMAs
+            mma(0, af, bfr);
+            frags_wait(cnt0{}, 1, af, bfr);  // every read of the stage is done before the next barrier
+            mma(1, af, bfr);
         }
     }
     wait_vmcnt<0>();  // drain the tail DMA before the workgroup may exit / LDS be reused
@@ -751,7 +838,18 @@ static hipError_t launch_gemm_cfg(const void* A, int lda, const void* W, int ldw
                                   const GemmEpi& ep, hipStream_t stream) {
     g_tile_count[BM <= 32 ? 0 : BM <= 64 ? 1 : BM <= 128 ? 2 : 3][BN <= 64 ? 0 : BN <= 96 ? 1 : BN <= 128 ? 2 : 3]
         .fetch_add(1, std::memory_order_relaxed);
-    const int tiles = ((M + BM - 1) / BM) * (N / BN) * (EPI == EPI_PARTIAL ? ep.split_k : 1);
+    const int nsplit = EPI == EPI_PARTIAL ? ep.split_k : 1;
+    GemmGeo geo;
+    geo.M = M;
+    geo.tiles_m = (M + BM - 1) / BM;
+    geo.tiles = geo.tiles_m * (N / BN);
+    if ((long)geo.tiles * nsplit >= (1l << 30)) return hipErrorInvalidValue;  // magic_div's range
+    geo.nwg = geo.tiles * nsplit;
+    magic_div_setup((unsigned)geo.tiles, &geo.sp_mul, &geo.sp_shift);
+    magic_div_setup((unsigned)geo.tiles_m, &geo.tm_mul, &geo.tm_shift);
+    geo.k_len = K / nsplit;
+    geo.nk = geo.k_len / (IN == IN_FP8 ? 2 * GEMM_BK : GEMM_BK);
+    const int tiles = geo.nwg;
     size_t lds = (size_t)STAGES * (BM + BN) * GEMM_BK * 2;  // 128-B rows for both input types
     const size_t stage_out = (size_t)BM * (BN * (EPI == EPI_PARTIAL ? 4 : 2) + 16);  // LDS-staged epilogue
     if (EPI != EPI_ARGMAX && EPI != EPI_F32 && stage_out > lds) lds = stage_out;
@@ -760,8 +858,7 @@ static hipError_t launch_gemm_cfg(const void* A, int lda, const void* W, int ldw
                                   (int)lds); e != hipSuccess)
         return e;
     hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE>), dim3(tiles), dim3(64 * WM * WN), lds, stream, A,
-                       lda, W,
-                       ldw, M, N, K, ep);
+                       W, lda, ldw, geo, N, ep);
     return hipGetLastError();
 }
 
