@@ -205,7 +205,10 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(const bf16_t* __restrict
 
 // Persistent, low-occupancy variant of attn_wave_kernel for the overlapped decode step: a fixed
 // grid of NB workgroups x 4 waves, each wave looping over (row, head) pairs (consecutive pairs = the
-// heads of one row, adjacent in the cache).  An 8-deep unroll keeps 16 KiB of K/V in flight per wave
+// heads of one row, adjacent in the cache).  An 8-deep unroll asks for 16 KiB of K/V per wave and
+// block of keys (as compiled, 8 KiB are in flight at a time: the V loads, used only under the block
+// update's condition, are emitted inside it, behind the scores; issuing them with the K loads made
+// the kernel 1 us faster and the two-stream step 0.5 % slower, docs/PERFORMANCE.md round 8),
 // so ~8 waves per CU still stream HBM at full rate -- and leave the CU's other wave slots, LDS and
 // MFMA pipes to the GEMMs of the other row half running on the second stream (a one-wave-per-pair
 // grid of 6k waves occupies every slot and serialises the two streams at kernel granularity).

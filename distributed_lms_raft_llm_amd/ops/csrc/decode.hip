@@ -24,23 +24,45 @@ __global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ toke
     }
 }
 
-// max over a row's partial argmax keys, one wave per row (keys(b, p) = keys[b * sb + p * sp])
+// max over a row's partial argmax keys, one wave per row (keys(b, p) = keys[b * sb + p * sp]), in
+// rounds of 16 keys per lane.  The LM head leaves ~800 partial keys per row at TP=1: one round.
+// A round's loads are unconditional -- the index is clamped to the last key and the value masked
+// afterwards -- so all 16 issue back to back behind one wait.  (Guarded as `p < nparts ? keys[..] : 0`
+// the compiler emits branch, load, full wait per key: a load is never hoisted out of a
+// data-dependent condition.  The fix add_layernorm_kernel documents for itself.)
+#define KEY_ROUND 16
+__device__ __forceinline__ void key_round_load(const unsigned long long* __restrict__ keys, int b, int nparts,
+                                               long long sb, long long sp, int lane, int p0,
+                                               unsigned long long (&k)[KEY_ROUND]) {
+#pragma unroll
+    for (int u = 0; u < KEY_ROUND; ++u) {
+        const int p = p0 + lane + 64 * u;
+        k[u] = keys[(size_t)b * sb + (size_t)(p < nparts ? p : nparts - 1) * sp];
+    }
+}
+__device__ __forceinline__ unsigned long long key_round_max(const unsigned long long (&k)[KEY_ROUND], int nparts,
+                                                            int lane, int p0, unsigned long long best) {
+#pragma unroll
+    for (int u = 0; u < KEY_ROUND; ++u) {
+        const unsigned long long v = p0 + lane + 64 * u < nparts ? k[u] : 0ull;
+        best = v > best ? v : best;
+    }
+    return best;
+}
+// rounds from p0 on, folded into `best` (per lane; the caller reduces across the wave)
+__device__ __forceinline__ unsigned long long key_rounds_from(const unsigned long long* __restrict__ keys, int b,
+                                                              int nparts, long long sb, long long sp, int lane,
+                                                              int p0, unsigned long long best) {
+    for (; p0 < nparts; p0 += 64 * KEY_ROUND) {
+        unsigned long long k[KEY_ROUND];
+        key_round_load(keys, b, nparts, sb, sp, lane, p0, k);
+        best = key_round_max(k, nparts, lane, p0, best);
+    }
+    return best;
+}
 __device__ __forceinline__ unsigned long long wave_key_max(const unsigned long long* __restrict__ keys, int b,
                                                            int nparts, long long sb, long long sp, int lane) {
-    // 16 independent loads in flight per lane per round: the LM head leaves ~800 partial keys per
-    // row at TP=1, one round trip (a one-load-at-a-time loop paid ~13 dependent round trips)
-    unsigned long long best = 0ull;
-    for (int p0 = 0; p0 < nparts; p0 += 64 * 16) {
-        unsigned long long k[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int p = p0 + lane + 64 * u;
-            k[u] = p < nparts ? keys[(size_t)b * sb + (size_t)p * sp] : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) best = k[u] > best ? k[u] : best;
-    }
-    return wave_max_u64(best);  // identical in every lane
+    return wave_max_u64(key_rounds_from(keys, b, nparts, sb, sp, lane, 0, 0ull));  // identical in every lane
 }
 
 // argmax partials [B][nparts] -> one key per row (before the cross-rank all-gather under TP)
@@ -64,9 +86,11 @@ __global__ __launch_bounds__(256) void argmax_reduce_kernel(const unsigned long 
 // Writes the next forward's token/position/kv-length for row b and its embedding into x.
 // slot_map (optional): key row i updates sequence slot slot_map[i] -- used when a prefill of new
 // requests lands in arbitrary free slots of a running continuous batch.
-// Dependency chain: everything that does not depend on the new token -- the row's length and stop
-// flag, its positional-embedding row, a finished row's last token -- is loaded together with the
-// keys, so the step pays two memory round trips (keys -> token embedding row), not five.
+// Dependency chain: three memory round trips -- (1) the row's length and stop flag together with the
+// first round of keys, (2) what the length addresses (positional-embedding row, a finished row's
+// last token) together with the LayerNorm weights, (3) the token's embedding row.  Every load of a
+// batch is unconditional (clamped index, value masked or unused afterwards): a load under a
+// per-lane condition is emitted as branch, load, full wait, which made each batch a chain of its own.
 __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long long* __restrict__ keys, int nparts,
                                                             long long sb, long long sp,
                                                             const int* __restrict__ slot_map, int* lens,
@@ -86,21 +110,39 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     // row state (every lane reads the same words: one request each)
     const int len0 = (int)dlms_idx(lens[b], max_len + 1, CHK_UPDATE_LEN);
     const int fin = finished[b];
+    unsigned long long k0[KEY_ROUND];  // in flight with lens / finished
+    key_round_load(keys, i, nparts, sb, sp, lane, 0, k0);
+    __builtin_amdgcn_sched_barrier(0);  // (the scheduler would otherwise move them behind the wait for len0)
     // where a live row's token goes (a finished row may sit at len == max_len: not an index then)
     const int live_len = fin ? 0 : (int)dlms_idx(len0, max_len, CHK_UPDATE_LEN);
     int pos = fin ? len0 - 1 : live_len;  // (length after this step) - 1
     pos = pos < 0 ? 0 : (pos < t_max - 1 ? pos : t_max - 1);
-    const int last_tok = fin ? out_tokens[(size_t)b * max_len + (len0 > 0 ? len0 - 1 : 0)] : 0;
+    // (a live row's len0 - 1 is a valid index too: read it anyway, use it only for a finished row)
+    const int prev_tok = out_tokens[(size_t)b * max_len + (len0 > 0 ? len0 - 1 : 0)];
+    const int last_tok = fin ? prev_tok : 0;
     // the row in float4 chunks c = lane + 64 j -- add_layernorm_kernel's partition, so the fused
-    // LayerNorm below computes exactly what that kernel would on the stored row
+    // LayerNorm below computes exactly what that kernel would on the stored row; chunks past the
+    // row (c >= nv) read the row's last chunk and are never used
     const int nv = D >> 2;
     uint2 pe[DU_MAXV4];
 #pragma unroll
     for (int j = 0; j < DU_MAXV4; ++j) {
-        const int c = lane + 64 * j;
-        pe[j] = c < nv ? *reinterpret_cast<const uint2*>(wpe + (size_t)pos * D + c * 4) : make_uint2(0u, 0u);
+        const int c = lane + 64 * j < nv ? lane + 64 * j : nv - 1;
+        pe[j] = *reinterpret_cast<const uint2*>(wpe + (size_t)pos * D + c * 4);
     }
-    const unsigned long long best = wave_key_max(keys, i, nparts, sb, sp, lane);
+    // LayerNorm weights with the same batch (without the fused LayerNorm the lanes read the row's
+    // own x, valid and unused, so that the loads need no branch)
+    const float4* gsrc = reinterpret_cast<const float4*>(h ? ln_g : x + (size_t)b * ldx);
+    const float4* bsrc = reinterpret_cast<const float4*>(h ? ln_b : x + (size_t)b * ldx);
+    float4 lg[DU_MAXV4], lb[DU_MAXV4];
+#pragma unroll
+    for (int j = 0; j < DU_MAXV4; ++j) {
+        const int c = lane + 64 * j < nv ? lane + 64 * j : nv - 1;
+        lg[j] = gsrc[c];
+        lb[j] = bsrc[c];
+    }
+    const unsigned long long best = wave_max_u64(
+        key_rounds_from(keys, i, nparts, sb, sp, lane, 64 * KEY_ROUND, key_round_max(k0, nparts, lane, 0, 0ull)));
 
     int tok;
     if (!fin) {
@@ -125,12 +167,16 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     const bf16_t* a = wte + (size_t)tok * D;
     float4* o = reinterpret_cast<float4*>(x + (size_t)b * ldx);
     float4 v[DU_MAXV4];
+    uint2 te[DU_MAXV4];
+#pragma unroll
+    for (int j = 0; j < DU_MAXV4; ++j)
+        te[j] = *reinterpret_cast<const uint2*>(a + (lane + 64 * j < nv ? lane + 64 * j : nv - 1) * 4);
 #pragma unroll
     for (int j = 0; j < DU_MAXV4; ++j) {
         const int c = lane + 64 * j;
         v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c >= nv) continue;
-        const uint2 e = *reinterpret_cast<const uint2*>(a + c * 4);
+        const uint2 e = te[j];
         v[j] = make_float4(bf16_to_f32((bf16_t)(e.x & 0xffffu)) + bf16_to_f32((bf16_t)(pe[j].x & 0xffffu)),
                            bf16_to_f32((bf16_t)(e.x >> 16)) + bf16_to_f32((bf16_t)(pe[j].x >> 16)),
                            bf16_to_f32((bf16_t)(e.y & 0xffffu)) + bf16_to_f32((bf16_t)(pe[j].y & 0xffffu)),
@@ -157,7 +203,7 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     for (int j = 0; j < DU_MAXV4; ++j) {
         const int c = lane + 64 * j;
         if (c >= nv) continue;
-        const float4 g = reinterpret_cast<const float4*>(ln_g)[c], be = reinterpret_cast<const float4*>(ln_b)[c];
+        const float4 g = lg[j], be = lb[j];
         uint2 pk;
         pk.x = pack_bf16x2((v[j].x - mean) * rstd * g.x + be.x, (v[j].y - mean) * rstd * g.y + be.y);
         pk.y = pack_bf16x2((v[j].z - mean) * rstd * g.z + be.z, (v[j].w - mean) * rstd * g.w + be.w);

@@ -61,6 +61,17 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// A 4-byte global load as a bare instruction (base + 32-bit byte offset), for values the epilogue
+// needs: written as plain C++ the compiler sinks such a load into the block that uses it, behind
+// the K loop, where its round trip is exposed.  The value may be used only behind a wait_vmcnt that
+// covers it, released by global_value_release() behind that wait.
+__device__ __forceinline__ unsigned global_load_b32_nowait(const void* base, unsigned byte_off) {
+    unsigned v;
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(byte_off), "s"(base) : "memory");
+    return v;
+}
+__device__ __forceinline__ void global_value_release(unsigned& v) { asm volatile("" : "+v"(v)); }
+
 // Main loop: K advances in 64-deep steps through a STAGES-deep LDS ring (STAGES-1 steps of loads in
 // flight: the decode GEMMs are HBM-latency-bound, so the ring is as deep as the LDS allows) filled by
 // global_load_lds_dwordx4 (LDS-DMA, no staging registers).  Each 1-KiB wave-instruction lands 8 tile
@@ -89,22 +100,22 @@ __device__ __forceinline__ void wait_vmcnt() {
 #define GROUP_M 4
 // Write-out of an LDS-staged bf16 QKV tile (rows [r0, r0 + CHUNKS / CPR), columns from c0, CPR
 // 16-B chunks per row): q columns go to q_out, K/V columns to each row's cache slot / position.
-// Every chunk's slot / position index is loaded before the first store -- interleaved with the
-// stores they cost one dependent L2 round trip per chunk (3-8 per thread per tile).
+// Chunk `it` of a thread belongs to row qkv_chunk_row() (clamped into the tile and into M, so its
+// slot / position index can be read unconditionally); the caller passes every chunk's indices in
+// sl / ps, read before the first store -- interleaved with the stores they cost one dependent L2
+// round trip per chunk (3-8 per thread per tile).
 template <int CHUNKS, int NT, int CPR>
-__device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int tid, int r0, int c0, int M,
-                                                 const GemmEpi& ep) {
+__device__ __forceinline__ int qkv_chunk_row(int tid, int it, int r0, int M) {
+    int c = tid + it * NT;
+    c = c < CHUNKS ? c : CHUNKS - 1;
+    const int row = r0 + c / CPR;
+    return row < M ? row : M - 1;
+}
+template <int CHUNKS, int NT, int CPR>
+__device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow, int tid, int r0, int c0, int M,
+                                                     const GemmEpi& ep, const int (&sl)[(CHUNKS + NT - 1) / NT],
+                                                     const int (&ps)[(CHUNKS + NT - 1) / NT]) {
     constexpr int ITER = (CHUNKS + NT - 1) / NT;
-    int sl[ITER], ps[ITER];
-#pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-        int c = tid + it * NT;
-        c = c < CHUNKS ? c : CHUNKS - 1;
-        int row = r0 + c / CPR;
-        row = row < M ? row : M - 1;
-        sl[it] = ep.row_slot[row];
-        ps[it] = ep.row_pos[row];
-    }
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int c = tid + it * NT;
@@ -127,6 +138,20 @@ __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int
         }
         *reinterpret_cast<uint4*>(dst) = val;
     }
+}
+// ... with the indices loaded here, in one batch ahead of the stores (the 256x256 prefill kernel)
+template <int CHUNKS, int NT, int CPR>
+__device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int tid, int r0, int c0, int M,
+                                                 const GemmEpi& ep) {
+    constexpr int ITER = (CHUNKS + NT - 1) / NT;
+    int sl[ITER], ps[ITER];
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int row = qkv_chunk_row<CHUNKS, NT, CPR>(tid, it, r0, M);
+        sl[it] = ep.row_slot[row];
+        ps[it] = ep.row_pos[row];
+    }
+    qkv_staged_store_idx<CHUNKS, NT, CPR>(smem, srow, tid, r0, c0, M, ep, sl, ps);
 }
 
 // Launch geometry, computed once on the host (launch_gemm_cfg) so that the kernel's prologue holds no
@@ -250,6 +275,55 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
 
     const int wm = wave / WN;
     const int wn = wave % WN;
+
+    // Everything the LDS-staged epilogue of the 64-row decode tiles reads from memory is requested
+    // here, behind the prologue's DMA, and held in registers across the K loop: the lane's TN bias
+    // values and, for EPI_QKV, the slot / position indices of its staged chunks (their rows depend
+    // only on tid and m0).  Written as plain loads in the epilogue, the compiler emits them behind
+    // the last MFMA, each bias column behind a full wait of its own.  They are consumed behind the
+    // wait_vmcnt<0>() that follows the loop.  The loop's counted vmcnt waits stay correct with these
+    // loads outstanding: vmcnt(N) leaves at most the N youngest loads in flight, the step it waits
+    // for has N younger DMAs behind it by construction, so additional loads of any age can only make
+    // it retire more, never less.
+    constexpr bool EPF = !REGPF && IN == IN_BF16 && BM <= 64 &&
+                         (EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF || EPI == EPI_PARTIAL ||
+                          EPI == EPI_QKV);
+    constexpr bool EPF_BIAS = EPF && EPI != EPI_PARTIAL;
+    constexpr int QCPR = BN * 2 / 16;                          // 16-B chunks per staged bf16 tile row
+    constexpr int QITER = (BM * QCPR + NT - 1) / NT;           // staged chunks per thread
+    unsigned bias_pf[TN], sl_pf[QITER], ps_pf[QITER];
+    if constexpr (EPF) {
+        // The epilogue's kernel-argument fields, read (s_load) here as well, not behind the loop.
+        // lgkmcnt also counts scalar loads, which return out of order: the loop's lgkmcnt(TM + TN)
+        // fragment waits are valid only with no scalar load outstanding, hence the full wait behind
+        // them (its latency sits under the first DMA wait).
+        if constexpr (EPI == EPI_QKV)
+            asm volatile("" ::"s"(ep.bias), "s"(ep.row_slot), "s"(ep.row_pos), "s"(ep.q_out), "s"(ep.k_cache),
+                         "s"(ep.v_cache), "s"(ep.ldq), "s"(ep.d_local), "s"(ep.n_heads), "s"(ep.t_max));
+        else if constexpr (EPI == EPI_PARTIAL)
+            asm volatile("" ::"s"(ep.out), "s"(ep.ldo), "s"(ep.split_stride));
+        else
+            asm volatile("" ::"s"(ep.bias), "s"(ep.out), "s"(ep.ldo));
+        wait_lgkmcnt<0>();
+        if constexpr (EPF_BIAS) {
+            // branch-free (a load under a condition would put a register copy between the load and
+            // its wait): without a bias the lanes read the first word of A and the value is dropped
+            const void* bbase = ep.bias ? static_cast<const void*>(ep.bias) : A;
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                bias_pf[j] = global_load_b32_nowait(
+                    bbase, ep.bias ? (unsigned)(n0 + wn * WTN + (lane & 15) + j * 16) * 4u : 0u);
+        }
+        if constexpr (EPI == EPI_QKV) {
+#pragma unroll
+            for (int it = 0; it < QITER; ++it) {
+                const unsigned off = (unsigned)qkv_chunk_row<BM * QCPR, NT, QCPR>(tid, it, m0, M) * 4u;
+                sl_pf[it] = global_load_b32_nowait(ep.row_slot, off);
+                ps_pf[it] = global_load_b32_nowait(ep.row_pos, off);
+            }
+        }
+    }
+
     f32x4_t acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -388,6 +462,17 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
         }
     }
     wait_vmcnt<0>();  // drain the tail DMA before the workgroup may exit / LDS be reused
+    if constexpr (EPF_BIAS) {  // ... and the epilogue operands requested ahead of the loop
+#pragma unroll
+        for (int j = 0; j < TN; ++j) global_value_release(bias_pf[j]);
+    }
+    if constexpr (EPF && EPI == EPI_QKV) {
+#pragma unroll
+        for (int it = 0; it < QITER; ++it) {
+            global_value_release(sl_pf[it]);
+            global_value_release(ps_pf[it]);
+        }
+    }
 
     if constexpr (IN == IN_FP8) {  // dequantise: per-row activation scale x per-channel weight scale
         const int rb = m0 + wm * WTM + (lane >> 4) * 4;
@@ -484,7 +569,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
         const int lcol0 = wn * WTN + (lane & 15);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const float bv = (EPI != EPI_PARTIAL && ep.bias) ? ep.bias[n0 + lcol0 + j * 16] : 0.f;
+            float bv;
+            if constexpr (EPF_BIAS)
+                bv = ep.bias ? __uint_as_float(bias_pf[j]) : 0.f;
+            else
+                bv = (EPI != EPI_PARTIAL && ep.bias) ? ep.bias[n0 + lcol0 + j * 16] : 0.f;
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -501,7 +590,15 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
         }
         __syncthreads();
         if constexpr (EPI == EPI_QKV) {
-            qkv_staged_store<BM * CPR, NT, CPR>(smem, SROW, tid, m0, n0, M, ep);
+            if constexpr (EPF) {
+                static_assert(CPR == QCPR, "the prefetched indices follow the staged chunk map");
+                int sl[QITER], ps[QITER];
+#pragma unroll
+                for (int it = 0; it < QITER; ++it) sl[it] = (int)sl_pf[it], ps[it] = (int)ps_pf[it];
+                qkv_staged_store_idx<BM * CPR, NT, CPR>(smem, SROW, tid, m0, n0, M, ep, sl, ps);
+            } else {
+                qkv_staged_store<BM * CPR, NT, CPR>(smem, SROW, tid, m0, n0, M, ep);
+            }
             return;
         }
         for (int c = tid; c < BM * CPR; c += NT) {

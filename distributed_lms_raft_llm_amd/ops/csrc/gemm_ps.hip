@@ -109,19 +109,26 @@ __global__ __launch_bounds__(64 * PS_NW) void gemm_ps_kernel(const bf16_t* __res
 
     char* stage = smem + BM * row_bytes + wave * PS_STAGE;
 
-    auto finish_tile = [&](int step, unsigned int swl, unsigned int swl2) {
+    // argmax: the seen-bitmap words of the tile's rows, exchanged through the wave's staging region
+    // (unused by this epilogue otherwise): word of row l at seen_stage[l]
+    unsigned int* seen_stage = reinterpret_cast<unsigned int*>(stage);
+    static_assert(16 * 8 * 4 <= PS_STAGE, "the staging region holds a seen word per panel row");
+
+    auto finish_tile = [&](int step) {
         const int tile = slot + (step / nch) * slots;
         const int col0 = tile * NT * 16;  // first column of the tile
         if constexpr (EPI == PS_ARGMAX) {
+            // the tile's (<= 32) columns share one seen-bitmap word per row; this lane's rows
+            // 16i + 4g + r, r = 0..3, are four consecutive words: MT 16-B reads behind one wait
+            // (16 dependent cross-lane shuffles, each with a wait of its own, before)
+            uint4 sw[MT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) sw[i] = *reinterpret_cast<const uint4*>(seen_stage + 16 * i + 4 * g);
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    // the tile's (<= 32) columns share one seen-bitmap word per row; lane (g, 4i + r)
-                    // loaded the word of row 16i + 4g + r
-                    // (row tiles 4.. of an 80-row panel: the second word, swl2)
-                    const unsigned int bits = i < 4 ? __shfl(swl, g * 16 + 4 * i + r, 64)
-                                                    : __shfl(swl2, g * 16 + 4 * (i - 4) + r, 64);
+                    const unsigned int bits = r == 0 ? sw[i].x : r == 1 ? sw[i].y : r == 2 ? sw[i].z : sw[i].w;
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         const int gcol = col0 + 16 * t + fr + ep.col_offset;
@@ -199,24 +206,27 @@ __global__ __launch_bounds__(64 * PS_NW) void gemm_ps_kernel(const bf16_t* __res
             for (int t = 0; t < NT; ++t) acc[i][t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     };
 
-    auto compute = [&](const bf16x8_t (&b)[KBC][NT], int step) {
-        const int kb0 = (step % nch) * KBC;
-        unsigned int swl = 0, swl2 = 0;
-        if constexpr (EPI == PS_ARGMAX) {
-            // one seen-bitmap word per lane per chunk (unconditional: a static load count keeps the
-            // counted vmcnt of the double-buffered weight stream); its latency hides under the MFMAs
-            const int tile = slot + (step / nch) * slots;
-            int srow = m0 + 16 * (fr >> 2) + 4 * g + (fr & 3);
-            srow = srow < M ? srow : M - 1;
-            swl = ep.seen[(size_t)srow * ep.seen_words + ((tile * NT * 16 + ep.col_offset) >> 5)];
-            static_assert(NT <= 2, "a tile's columns share one seen word per row");
-            if constexpr (MT > 4) {  // a lane's word covers row tiles 0..3; tiles 4..7 take a second one
-                static_assert(MT <= 8, "two seen words per lane cover at most 8 row tiles");
-                int srow2 = m0 + 16 * ((fr >> 2) + 4) + 4 * g + (fr & 3);
-                srow2 = srow2 < M ? srow2 : M - 1;
-                swl2 = ep.seen[(size_t)srow2 * ep.seen_words + ((tile * NT * 16 + ep.col_offset) >> 5)];
-            }
+    // argmax: one seen-bitmap word per lane per chunk (lane l: panel row l; an 80-row panel's rows
+    // 64.. take a second word), requested AHEAD of the next chunk's weight loads and unconditional: a
+    // static load count keeps the counted vmcnt of the double-buffered weight stream.  compute()
+    // stores it to the staging region behind the chunk's MFMAs, every chunk: used only by
+    // finish_tile, the load is sunk into that conditional block, behind the tile's last MFMA and
+    // behind a vmcnt(0) that also drains the prefetched weights.
+    auto seen_load = [&](int step, unsigned int& swl, unsigned int& swl2) {
+        const int tile = slot + (step / nch) * slots;
+        const int word = (tile * NT * 16 + ep.col_offset) >> 5;
+        static_assert(NT <= 2, "a tile's columns share one seen word per row");
+        static_assert(MT <= 8, "two seen words per lane cover at most 8 row tiles");
+        const int srow = m0 + lane < M ? m0 + lane : M - 1;
+        swl = ep.seen[(size_t)srow * ep.seen_words + word];
+        if constexpr (MT > 4) {
+            const int srow2 = m0 + 64 + lane < M ? m0 + 64 + lane : M - 1;
+            swl2 = ep.seen[(size_t)srow2 * ep.seen_words + word];
         }
+    };
+
+    auto compute = [&](const bf16x8_t (&b)[KBC][NT], int step, unsigned int swl, unsigned int swl2) {
+        const int kb0 = (step % nch) * KBC;
 #pragma unroll
         for (int kb = 0; kb < KBC; ++kb) {
             bf16x8_t a[MT];
@@ -228,7 +238,13 @@ __global__ __launch_bounds__(64 * PS_NW) void gemm_ps_kernel(const bf16_t* __res
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[kb][t], acc[i][t], 0, 0, 0);
         }
-        if (step % nch == nch - 1) finish_tile(step, swl, swl2);
+        if constexpr (EPI == PS_ARGMAX) {
+            // (wave-private, and a wave's LDS accesses complete in order: no barrier; the last
+            // tile's reads of these words were issued before this store)
+            seen_stage[lane] = swl;
+            if constexpr (MT > 4) seen_stage[64 + lane] = swl2;
+        }
+        if (step % nch == nch - 1) finish_tile(step);
     };
 
     // register ring of weight chunks: NBUF-1 chunks in flight behind the one being computed.  The
@@ -249,8 +265,10 @@ __global__ __launch_bounds__(64 * PS_NW) void gemm_ps_kernel(const bf16_t* __res
 #pragma unroll
         for (int j = 0; j < NBUF; ++j) {  // (compile-time buffer indices: the ring stays in registers)
             if (j > 0 && step + j >= nsteps) break;
+            unsigned int swl = 0, swl2 = 0;
+            if constexpr (EPI == PS_ARGMAX) seen_load(step + j, swl, swl2);
             load(b[(j + NBUF - 1) % NBUF], step + j + NBUF - 1);
-            compute(b[j], step + j);
+            compute(b[j], step + j, swl, swl2);
         }
     }
 
@@ -293,7 +311,7 @@ extern "C" hipError_t dlms_gemm_ps(int epi, const void* A, int lda, const void* 
         return hipErrorInvalidValue;
     if (epi != PS_PARTIAL && split != 1) return hipErrorInvalidValue;
     // the argmax LM head (64 x 32 wave tiles): 8-k-block register chunks, double-buffered -- 16 KiB
-    // of weights in flight per wave instead of 8 (232 VGPRs, no scratch): M = 512 67.5 -> 64.0 us,
+    // of weights in flight per wave instead of 8 (238 VGPRs, no scratch): M = 512 67.5 -> 64.0 us,
     // M = 1024 107.9 -> 99.7 us (profiles/r5_lmhead_kbc_ab.jsonl; 6-k-block chunks x 3 buffers and
     // 64 x 64 wave tiles on 4-k-block chunks measured 68.2 / 64.1 us, both with spills)
     if (epi == PS_ARGMAX && mt == 4 && nt == 2 && (K / split) % (32 * 8) == 0)
