@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..models.config import GPT2Config
+from ..models.config import GPT2Config, SamplingParams
 from ..utils.metrics import METRICS
 from .weights import GPT2DeviceWeights, prepare_gpt2_weights
 
@@ -169,6 +169,17 @@ def _bucket(n: int) -> int:
         if n <= b:
             return b
     return (n + 255) // 256 * 256
+
+
+def sampling_unsupported(tp_size: int, fp8: bool) -> str | None:
+    """Why an engine of this shape cannot sample (None: it can)."""
+    if tp_size > 1:
+        return ("sampling is not supported with tensor parallelism (tp_size > 1): the device sampler ranks one "
+                "rank's whole vocabulary; serve greedy or TP=1")
+    if fp8:
+        return ("sampling is not supported with fp8 weights: the fp8 LM head has no f32-logits epilogue; serve "
+                "greedy or weight_dtype='bf16'")
+    return None
 
 
 class HipGPT2Engine:
@@ -422,6 +433,12 @@ class HipGPT2Engine:
         self._side_streams: list[torch.cuda.Stream] = []
         self._flags: torch.Tensor | None = None
         self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
+        # sampling (None: greedy): the parameters of the public call in progress (_sampling_scope);
+        # the f32 logits scratch of the sampled LM head, allocated on the first sampled call
+        self._sampling: SamplingParams | None = None
+        self._logits: torch.Tensor | None = None
+        self._rng_seed_host: int | None = None  # the seed in rng_seed (None: never set)
+        self._rng_count = 0  # requests admitted since the seed was last set: the next stream id
         self._alloc_state()
         self.xgmi = None
         if self.tp_size > 1:
@@ -477,6 +494,10 @@ class HipGPT2Engine:
         self.cur_pos = torch.zeros(B, dtype=i32, device=dev)
         self.cur_kvlen = torch.ones(B, dtype=i32, device=dev)
         self.slots = torch.arange(B, dtype=i32, device=dev)
+        # sampler RNG state, on the device so that graph replays do not bake it in: the seed word
+        # and every slot's request stream id (written at admission)
+        self.rng_seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.rng_stream = torch.zeros(B, dtype=torch.int64, device=dev)
         self._reset_slots(0, B)
 
     def kv_cache_bytes(self) -> int:
@@ -673,14 +694,35 @@ class HipGPT2Engine:
     def _lm_head_and_update(self, hidden: torch.Tensor | None, B: int, penalty: float, seen: torch.Tensor | None = None,
                             hscale: torch.Tensor | None = None, slot_map: torch.Tensor | None = None, lo: int = 0,
                             ln1_out: torch.Tensor | None = None):
-        """LM head with the fused penalty + argmax on ``hidden`` (bf16, or e4m3 with ``hscale``),
-        then the greedy bookkeeping.  Rows map to slots [lo, lo + B) or through ``slot_map``.
+        """LM head with the fused penalty + argmax on ``hidden`` (bf16, or e4m3 with ``hscale``) --
+        inside a ``_sampling_scope``: f32 logits and the device sampler instead -- then the
+        bookkeeping of the chosen token.  Rows map to slots [lo, lo + B) or through ``slot_map``.
         ``ln1_out`` (rows [lo, lo + B)): the update also writes layer 0's LN1 of the new rows there."""
         cfg = self.cfg
         hi = lo + B
         seen_rows = self.seen[lo:hi] if seen is None else seen
         P = self.key_parts.shape[1]  # partial keys per row the LM head writes (and the consumer reads)
-        if hidden.dtype != ops.FP8 and self.ps_lm and B >= self.PS_LM_MIN_ROWS:
+        sp = self._sampling
+        if sp is not None:
+            # sampling: raw f32 logits (the GEMMs' plain f32 epilogues; the penalty moves into the
+            # sampler), then one drawn key per row in the first key column
+            self._check_sampling(sp)
+            if hidden.dtype == ops.FP8 or self._logits is None:
+                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope")
+            z = self._logits[lo:hi]
+            if self.ps_lm and B >= self.PS_LM_MIN_ROWS:
+                ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
+            else:
+                ops.gemm(hidden, self.w.lm_head, ops.EPI_F32, out=z)
+            P = 1
+            if slot_map is None:
+                ops.sample_topk_topp(z, seen_rows, self.lens[lo:hi], self.rng_stream[lo:hi], self.rng_seed, penalty,
+                                     sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi])
+            else:
+                ops.sample_topk_topp(z, seen_rows, self.lens, self.rng_stream, self.rng_seed, penalty,
+                                     sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi],
+                                     slot_map=slot_map)
+        elif hidden.dtype != ops.FP8 and self.ps_lm and B >= self.PS_LM_MIN_ROWS:
             P = ops.gemm_ps_key_slots(B, self.lm_head_sh.shape[0] * 16, self.lm_head_sh.shape[1] * 32)
             ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_ARGMAX, argmax_out=self.key_parts[lo:hi], seen=seen_rows,
                         vocab=cfg.vocab_size, col_offset=self.w.vocab_range[0], penalty=penalty)
@@ -708,6 +750,51 @@ class HipGPT2Engine:
             ops.decode_update(keys, self.lens, self.finished, self.out_tokens, self.seen, self.cur_tok, self.cur_pos,
                               self.cur_kvlen, self.w.wte, self.w.wpe, self.x, cfg.eos_token_id, self.max_length,
                               slot_map=slot_map)
+
+    # ------------------------------------------------------------------ sampling
+    @contextlib.contextmanager
+    def _sampling_scope(self, sampling: "SamplingParams | None"):
+        """The sampling parameters of one public call: every LM head issued (or captured) inside
+        samples with them; graphs are keyed by them.  None: greedy, exactly the calls made before."""
+        if sampling is not None:
+            self._check_sampling(sampling)
+            if self._logits is None:  # (outside any capture: graph pools must not own it)
+                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
+                                           device=self.device)
+        prev, self._sampling = self._sampling, sampling
+        try:
+            yield
+        finally:
+            self._sampling = prev
+
+    def _check_sampling(self, sampling):
+        if not isinstance(sampling, SamplingParams):
+            raise TypeError("sampling: a SamplingParams (models/config.py) or None")
+        why = sampling_unsupported(self.tp_size, self.w.fp8)
+        if why:
+            raise ValueError(why)
+
+    def reseed(self, seed: int):
+        """Set the sampler's seed word and restart the request count: the next request admitted
+        draws from stream 0."""
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed: an integer in [0, 2^64)")
+        self.rng_seed.fill_(seed - 2 ** 64 if seed >= 2 ** 63 else seed)  # (the int64 with the same bits)
+        self._rng_seed_host, self._rng_count = seed, 0
+
+    def _next_streams(self, n: int, sampling: "SamplingParams | None") -> list[int] | None:
+        """Stream ids of the next ``n`` requests under ``sampling`` (None: greedy, no ids)."""
+        if sampling is None:
+            return None
+        if self._rng_seed_host != sampling.seed:
+            self.reseed(sampling.seed)
+        first = self._rng_count
+        self._rng_count += n
+        return list(range(first, first + n))
+
+    def _skey(self) -> tuple:
+        return () if self._sampling is None else self._sampling.shape_key
 
     def _overlap_ok(self, B: int) -> bool:
         k = self.overlap_parts
@@ -777,7 +864,8 @@ class HipGPT2Engine:
         from ..ops.dataflow import MAX_ROWS
 
         # (the launch-per-op path serves row counts whose stream window outgrows the LDS ring)
-        return (self.dataflow and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
+        # (sampling: the dataflow kernel's LM head is greedy; launch-per-op serves those rows)
+        return (self.dataflow and self._sampling is None and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
                 and time.monotonic() >= self._df_off_until and self._df_decoder().fits(B))
 
     def _df_run(self, B: int, steps: int, penalty: float) -> bool:
@@ -1022,7 +1110,7 @@ class HipGPT2Engine:
             self._lm_head_and_update(self.h[:B], B, penalty, ln1_out=self.h[:B] if fuse else None)
 
     def _graph_for(self, B: int, penalty: float, nsteps: int = 1) -> torch.cuda.CUDAGraph:
-        key = (B, float(penalty), nsteps)
+        key = (B, float(penalty), nsteps) + self._skey()  # (the seed is a device word: not in the key)
         g = self._graphs.get(key)
         if g is None:
             # warm up on a side stream (kernel code objects loaded, RCCL comm initialised).  The
@@ -1074,9 +1162,11 @@ class HipGPT2Engine:
         self.cur_pos[lo:hi].zero_()
         self.cur_kvlen[lo:hi].fill_(1)
 
-    def _prefill_into(self, prompts: list[list[int]], slots: list[int], penalty: float):
+    def _prefill_into(self, prompts: list[list[int]], slots: list[int], penalty: float,
+                      streams: list[int] | None = None):
         """Packed variable-length prefill of ``prompts`` into KV-cache slots ``slots`` (any free
-        slots of a running batch), then the first greedy token of each: the LM head's argmax rows
+        slots of a running batch), then the first token of each (greedy, or drawn inside a
+        ``_sampling_scope``, then with the requests' stream ids ``streams``): the LM head's key rows
         map back to their slots through decode_update's slot map."""
         cfg, dev = self.cfg, self.device
         n = len(prompts)
@@ -1098,6 +1188,12 @@ class HipGPT2Engine:
             raise ValueError("prefill: token id out of range")
         pos_np = np.arange(R, dtype=np.int64) - np.repeat(ends - lens_np, lens_np)
         slot_np = np.repeat(np.asarray(slots, dtype=np.int64), lens_np)
+        if self._sampling is not None:
+            # the slots' stream ids, ahead of (and outside) a replayed prefill graph
+            if streams is None or len(streams) != n:
+                raise ValueError("prefill: one stream id per sampled prompt")
+            self.rng_stream.index_copy_(0, _to_device(np.asarray(slots), dev, np.int64),
+                                        _to_device(np.asarray(streams, dtype=np.uint64).view(np.int64), dev, np.int64))
         if self._prefill_graph_ok(R, n):
             return self._prefill_graphed(tok_np, pos_np, slot_np, ends - 1, np.asarray(slots), lens_np, penalty)
         tokens_d, pos_d, slot_d, last_d, slots_d, lens_d = (
@@ -1156,7 +1252,7 @@ class HipGPT2Engine:
             return False
         if self.tp_size > 1 and not self._tp_capturable(R):
             return False
-        key = (R, n)
+        key = (R, n) + self._skey()
         if key in self._pgraphs:
             return True
         if len(self._pseen) > 8192:  # shapes seen once: a bounded memory of candidates
@@ -1175,7 +1271,7 @@ class HipGPT2Engine:
 
     def _prefill_graphed(self, tok, pos, slot, last, slots, lens, penalty: float):
         R, n = tok.size, slots.size
-        key = (R, n)
+        key = (R, n) + self._skey()
         TB = R // 16 + n  # >= the tile count of any R rows in n prompts
         st = self._pgraphs.get(key)
         if st is None:
@@ -1212,10 +1308,10 @@ class HipGPT2Engine:
             st["graph"], st["penalty"] = g, penalty
         st["graph"].replay()
 
-    def _prefill(self, prompts: list[list[int]], B: int, penalty: float):
+    def _prefill(self, prompts: list[list[int]], B: int, penalty: float, streams: list[int] | None = None):
         """Static batch: prompts into slots [0, n), slots [n, B) inert."""
         self._reset_slots(len(prompts), B)
-        self._prefill_into(prompts, list(range(len(prompts))), penalty)
+        self._prefill_into(prompts, list(range(len(prompts))), penalty, streams)
 
     @torch.no_grad()
     def prefill_last_hidden(self, prompts: list[list[int]]) -> torch.Tensor:
@@ -1243,13 +1339,24 @@ class HipGPT2Engine:
 
     # ------------------------------------------------------------------ slot API (continuous batching)
     @torch.no_grad()
-    def admit(self, prompts: list[list[int]], slots: list[int], repetition_penalty: float = 1.2):
-        """Prefill new sequences into free ``slots`` of the running batch (first token included)."""
-        self._prefill_into([list(p) for p in prompts], list(slots), repetition_penalty)
+    def admit(self, prompts: list[list[int]], slots: list[int], repetition_penalty: float = 1.2,
+              sampling: SamplingParams | None = None):
+        """Prefill new sequences into free ``slots`` of the running batch (first token included).
+        ``sampling``: draw their tokens instead; each takes the next stream id (the count of requests
+        admitted since the seed was last set: ``reseed``, or a ``sampling.seed`` other than the
+        current one)."""
+        with self._sampling_scope(sampling):
+            self._prefill_into([list(p) for p in prompts], list(slots), repetition_penalty,
+                               self._next_streams(len(prompts), sampling))
 
     @torch.no_grad()
-    def decode(self, B: int, steps: int, repetition_penalty: float = 1.2):
-        """``steps`` greedy decode steps over slots [0, B) (finished/inert slots are no-ops)."""
+    def decode(self, B: int, steps: int, repetition_penalty: float = 1.2, sampling: SamplingParams | None = None):
+        """``steps`` decode steps over slots [0, B) (finished/inert slots are no-ops): greedy, or
+        sampled with ``sampling`` under the slots' stream ids (``admit``)."""
+        with self._sampling_scope(sampling):
+            self._decode(B, steps, repetition_penalty)
+
+    def _decode(self, B: int, steps: int, repetition_penalty: float):
         if B > self.max_batch or B not in (_bucket(B), self.max_batch):
             raise ValueError(f"decode: batch bucket {B} invalid")
         self._df_status = None
@@ -1270,10 +1377,16 @@ class HipGPT2Engine:
                 self._decode_step(B, repetition_penalty)
 
     @torch.no_grad()
-    def warm_decode_graphs(self, repetition_penalty: float = 1.2, max_batch: int | None = None) -> tuple[int, float]:
+    def warm_decode_graphs(self, repetition_penalty: float = 1.2, max_batch: int | None = None,
+                           sampling: SamplingParams | None = None) -> tuple[int, float]:
         """Capture the decode-step graphs ``decode()`` would capture on first use (one step and one
         replay's worth of steps per batch bucket up to ``max_batch``; the dataflow buckets need none)
-        so a server's first burst of queries does not pay the captures.  Returns (graphs, seconds)."""
+        so a server's first burst of queries does not pay the captures.  ``sampling``: the graphs of
+        that sampling mode.  Returns (graphs, seconds)."""
+        with self._sampling_scope(sampling):
+            return self._warm_decode_graphs(repetition_penalty, max_batch)
+
+    def _warm_decode_graphs(self, repetition_penalty: float, max_batch: int | None) -> tuple[int, float]:
         if not self.use_graph:
             return 0, 0.0
         t0 = time.perf_counter()
@@ -1369,30 +1482,48 @@ class HipGPT2Engine:
     # ------------------------------------------------------------------ public API
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
-                 stats: GenerateStats | None = None) -> list[list[int]]:
+                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None) -> list[list[int]]:
+        """Full sequences (prompt echoed) of ``prompts``: greedy, or with ``sampling`` drawn under
+        ``sampling.seed`` with prompt i on stream i -- set anew on every call, so equal calls return
+        equal outputs."""
+        if sampling is None:
+            return self._generate(prompts, max_length, repetition_penalty, stats, None)
+        with self._sampling_scope(sampling):
+            self.reseed(sampling.seed)
+            self._rng_count = len(prompts)
+            return self._generate(prompts, max_length, repetition_penalty, stats, list(range(len(prompts))))
+
+    def _generate(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
+                  stats: GenerateStats | None, streams: list[int] | None) -> list[list[int]]:
         T = self.max_length if max_length is None else max_length
         if T != self.max_length:
             raise ValueError(f"engine built for max_length={self.max_length}, got {T}")
         n = len(prompts)
         if n == 0:
             return []
+
+        def pick(idx):
+            return None if streams is None else [streams[i] for i in idx]
+
         done, run_idx, prompts = passthrough(prompts, T, self.cfg.eos_token_id)
         if len(run_idx) < n:
-            sub = self.generate([prompts[i] for i in run_idx], max_length, repetition_penalty, stats) if run_idx else []
+            sub = self._generate([prompts[i] for i in run_idx], max_length, repetition_penalty, stats,
+                                 pick(run_idx)) if run_idx else []
             for i, o in zip(run_idx, sub):
                 done[i] = o
             return done
         if n > self.max_batch:
             out: list[list[int]] = []
             for i in range(0, n, self.max_batch):
-                out += self.generate(prompts[i: i + self.max_batch], max_length, repetition_penalty, stats)
+                out += self._generate(prompts[i: i + self.max_batch], max_length, repetition_penalty, stats,
+                                      pick(range(i, min(n, i + self.max_batch))))
             return out
         B = min(_bucket(n), self.max_batch)  # (prompts are passthrough()'s normalised copies)
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
         ev2 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-        self._prefill(prompts, B, repetition_penalty)
+        self._prefill(prompts, B, repetition_penalty, streams)
         ev1.record()
         steps_max = T - min(len(p) for p in prompts) - 1
         if steps_max > 0 and self._df_ok(B) and self._df_run(B, steps_max, repetition_penalty):
@@ -1488,7 +1619,9 @@ class TorchGPT2Engine:
 
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
-                 stats: GenerateStats | None = None) -> list[list[int]]:
+                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None) -> list[list[int]]:
+        """``sampling``: tokens drawn by ``models.gpt2.reference_sample`` under ``sampling.seed``,
+        prompt i on stream i (the HIP engine's rule)."""
         from ..models.gpt2 import reference_generate
 
         T = self.max_length if max_length is None else max_length
@@ -1496,7 +1629,8 @@ class TorchGPT2Engine:
         prompts = [norm[i] for i in run_idx]
         t0 = time.perf_counter()
         if prompts:
-            gen = reference_generate(self.model, prompts, max_length=T, repetition_penalty=repetition_penalty)
+            gen = reference_generate(self.model, prompts, max_length=T, repetition_penalty=repetition_penalty,
+                                     sampling=sampling, streams=list(run_idx))
             for i, o in zip(run_idx, gen):
                 out[i] = o
         out_run = [out[i] for i in run_idx]

@@ -19,8 +19,9 @@ BUCKETS = (1, 2, 4, 8, 16, 32, 48, 64, 96, 128, 192, 256, 384, 512, 768, 1024, 1
            8192, 12288, 16384, 24576, 32768, 49152, 65536)
 
 
-def slot_bytes(cfg: GPT2Config, max_length: int, tp_size: int = 1, tp_rank: int = 0) -> int:
-    """Device bytes one decode slot costs on this rank (KV cache + per-sequence state)."""
+def slot_bytes(cfg: GPT2Config, max_length: int, tp_size: int = 1, tp_rank: int = 0, sampling: bool = False) -> int:
+    """Device bytes one decode slot costs on this rank (KV cache + per-sequence state;
+    ``sampling``: plus its row of the sampled LM head's f32 logits)."""
     h0, h1 = shard_range(cfg.n_head, tp_size, tp_rank)
     hl = h1 - h0
     dl = hl * cfg.head_dim
@@ -33,6 +34,8 @@ def slot_bytes(cfg: GPT2Config, max_length: int, tp_size: int = 1, tp_rank: int 
              + vshard // 64 * 8 + 8 + tp_size * 8     # argmax keys
              + 6 * 4 + max_length * 4                 # lens/flags/cur_*, output tokens
              + cfg.vocab_padded // 8)                 # repetition-penalty bitmap
+    if sampling:
+        state += cfg.vocab_padded * 4 + 8             # f32 logits row, request stream id
     return kv + state
 
 
@@ -42,8 +45,9 @@ def weight_bytes(cfg: GPT2Config, tp_size: int = 1) -> int:
 
 def plan_max_batch(cfg: GPT2Config, max_length: int, tp_size: int = 1, free_bytes: int | None = None,
                    weights_resident: bool = False, reserve_frac: float = 0.08, reserve_bytes: int = 4 * GIB,
-                   prefill_tokens: int = 32768, cap: int = 4096, device=None) -> int:
-    """Largest batch bucket (<= ``cap``) whose slots fit in the free HBM after the reserve."""
+                   prefill_tokens: int = 32768, cap: int = 4096, device=None, sampling: bool = False) -> int:
+    """Largest batch bucket (<= ``cap``) whose slots fit in the free HBM after the reserve
+    (``sampling``: slots sized for the sampling mode's logits buffer, ``slot_bytes``)."""
     if free_bytes is None:
         import torch
 
@@ -53,7 +57,7 @@ def plan_max_batch(cfg: GPT2Config, max_length: int, tp_size: int = 1, free_byte
         budget -= weight_bytes(cfg, tp_size)
     # transient prefill activations for ``prefill_tokens`` packed prompt tokens
     budget -= prefill_tokens * (cfg.n_embd * 4 * 9 + cfg.n_inner // tp_size * 2 + cfg.n_embd * 6)
-    per = slot_bytes(cfg, max_length, tp_size)
+    per = slot_bytes(cfg, max_length, tp_size, sampling=sampling)
     fit = int(budget // per) if budget > 0 else 0
     best = 0
     for b in BUCKETS:

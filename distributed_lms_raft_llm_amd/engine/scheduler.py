@@ -20,6 +20,7 @@ Engine protocol (``HipGPT2Engine`` implements it; tests use a CPU fake):
     max_batch, max_length, cfg.eos_token_id
     admit(prompts, slots, repetition_penalty)   prefill + first token into those slots
     decode(B, steps, repetition_penalty)        ``steps`` decode steps over slots [0, B)
+                                                (both with ``sampling=`` when the batcher samples)
     finished_flags(B) -> list[int]              per-slot stop flags
     collect(slots) -> list[list[int]]           prompt + generated tokens
     flags_async(B), collect_async(slots)        optional: the same as handles with .result()
@@ -90,10 +91,15 @@ class Overloaded(RuntimeError):
 
 class ContinuousBatcher:
     def __init__(self, engine, repetition_penalty: float = 1.2, chunk: int = 8, max_admit: int | None = None,
-                 name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0):
+                 name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0, sampling=None):
         """``max_queue``: queries allowed to wait for a free KV slot before ``submit`` raises
-        ``Overloaded`` (0 = unbounded; the tutoring servers default to one batch of slots)."""
+        ``Overloaded`` (0 = unbounded; the tutoring servers default to one batch of slots).
+        ``sampling`` (a ``SamplingParams``): tokens are drawn instead of greedy; it is forwarded to
+        the engine's ``admit`` / ``decode`` as ``sampling=`` -- only when set, so greedy engines are
+        called exactly as before."""
         self.engine = engine
+        self.sampling = sampling
+        self._mode = {} if sampling is None else {"sampling": sampling}
         self.max_queue = int(max_queue or 0)
         self.rejected = 0
         env_prio = os.environ.get("DLMS_BATCHER_STREAM_PRIORITY")
@@ -227,7 +233,7 @@ class ContinuousBatcher:
             if admits:
                 ta = time.perf_counter()
                 with roctx_range("prefill"):
-                    eng.admit([r.prompt for _, r in admits], [s for s, _ in admits], self.penalty)
+                    eng.admit([r.prompt for _, r in admits], [s for s, _ in admits], self.penalty, **self._mode)
                 TRACER.complete("tutor.admit", ta, cat="tutor", n=len(admits),
                                 tokens=sum(len(r.prompt) for _, r in admits))
                 t_first = time.perf_counter()  # prefill (first token included) is enqueued
@@ -256,7 +262,7 @@ class ContinuousBatcher:
                     taken[s] = min(steps, r.steps_left)
                     r.steps_left -= taken[s]
                 with roctx_range("decode_chunk"):
-                    eng.decode(B, steps, self.penalty)
+                    eng.decode(B, steps, self.penalty, **self._mode)
                     cur = (flags_async(eng, B), dict(self._active), health_async(eng), dataflow_status_async(eng),
                            taken)
                 self.steps += steps

@@ -100,12 +100,46 @@ def bert_config(name: str) -> BertConfig:
         raise ValueError(f"unknown BERT config {name!r}; choose from {sorted(BERT_CONFIGS)}") from e
 
 
+SAMPLING_MAX_TOP_K = 256  # candidates the device sampler ranks per row (ops/csrc/sample.hip)
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """Seeded temperature / top-k / top-p sampling (HF's warper order: temperature, top-k, then
+    top-p with ``min_tokens_to_keep=1``).  The draw of a token depends only on ``seed``, the
+    request's stream id and the token's position (Philox4x32-10), never on the batch around it."""
+
+    temperature: float = 0.7
+    top_k: int = 50
+    top_p: float = 0.9
+    seed: int = 0
+
+    def __post_init__(self):
+        import math
+
+        t, k, p, s = self.temperature, self.top_k, self.top_p, self.seed
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or not t > 0:
+            raise ValueError(f"temperature {t!r}: a finite number > 0")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= SAMPLING_MAX_TOP_K:
+            raise ValueError(f"top_k {k!r}: an integer in [1, {SAMPLING_MAX_TOP_K}]")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 < p <= 1:
+            raise ValueError(f"top_p {p!r}: a number in (0, 1]")
+        if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < 2 ** 64:
+            raise ValueError(f"seed {s!r}: an integer in [0, 2^64)")
+
+    @property
+    def shape_key(self) -> tuple:
+        """What a captured graph bakes in (the seed is a device word, not part of it)."""
+        return (float(self.temperature), int(self.top_k), float(self.top_p))
+
+
 @dataclass
 class GenerationConfig:
     """Decode semantics of the reference ``model.generate`` call (tutoring_server.py:21-29).
 
-    ``do_sample`` is unset there, so decoding is greedy; ``temperature``/``top_k``/
-    ``top_p`` are accepted and ignored for parity.
+    ``do_sample`` is unset there, so decoding is greedy by default.  With ``do_sample`` set,
+    ``sampling()`` gives the ``SamplingParams`` (``temperature``/``top_k``/``top_p`` and
+    ``seed``) that the engines, the scheduler and the tutor server take as ``sampling=``.
     """
 
     max_length: int = 150  # total length, prompt included
@@ -116,3 +150,9 @@ class GenerationConfig:
     top_p: float = 0.9
     eos_token_id: int | None = None
     extra: dict = field(default_factory=dict)
+    seed: int = 0
+
+    def sampling(self) -> "SamplingParams | None":
+        if not self.do_sample:
+            return None
+        return SamplingParams(self.temperature, self.top_k, self.top_p, self.seed)

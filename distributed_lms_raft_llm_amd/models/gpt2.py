@@ -160,9 +160,13 @@ def reference_generate(
     max_length: int = 150,
     repetition_penalty: float = 1.2,
     eos_token_id: int | None = None,
+    sampling=None,
+    streams: list[int] | None = None,
 ) -> list[list[int]]:
     """Batched greedy + repetition-penalty decode.  Returns full sequences (prompt
-    echoed, as ``generate`` does), each stopping at EOS (inclusive) or ``max_length``."""
+    echoed, as ``generate`` does), each stopping at EOS (inclusive) or ``max_length``.
+    ``sampling`` (a ``SamplingParams``): every token is drawn by ``reference_sample`` instead, row b
+    with stream id ``streams[b]`` (default b) at position = the index the token is written to."""
     cfg = model.cfg
     eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
     B = len(prompts)
@@ -190,8 +194,13 @@ def reference_generate(
     h_last = hidden[rows, last]
     while True:
         logits = model.logits(h_last)
-        logits = apply_repetition_penalty(logits, seen, repetition_penalty)
-        nxt = torch.argmax(logits, dim=-1)
+        if sampling is None:
+            nxt = torch.argmax(apply_repetition_penalty(logits, seen, repetition_penalty), dim=-1)
+        else:
+            z, sn = logits.float().cpu().numpy(), seen.cpu().numpy()
+            nxt = [0 if done[b] else reference_sample(z[b], sn[b], repetition_penalty, sampling,
+                                                      b if streams is None else streams[b], len(seqs[b]))[0]
+                   for b in range(B)]
         for b in range(B):
             if done[b]:
                 continue
@@ -285,4 +294,147 @@ def teacher_forced_check_batch(model: GPT2Reference, seqs: list[list[int]], prom
                     if s[pl + j] != want[j]:
                         r["mismatches"].append((pl + j, s[pl + j], want[j], margin[j]))
             out.append(r)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Sampling: the normative CPU definition of the device sampler (ops/csrc/sample.hip)
+# ---------------------------------------------------------------------------------------------
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key) -> tuple[int, int, int, int]:
+    """Philox4x32 with 10 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"):
+    ``counter`` 4 and ``key`` 2 32-bit words -> 4 32-bit words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def sampling_uniform(seed: int, stream: int, position: int) -> float:
+    """The draw u in [0, 1) of (seed, request stream id, token position): 24 bits of Philox word 0."""
+    r = philox4x32_10((position, stream & _M32, (stream >> 32) & _M32, 0), (seed & _M32, (seed >> 32) & _M32))
+    return (r[0] >> 8) * 2.0 ** -24
+
+
+def f32_ordered(x):
+    """Order-preserving map of float32 values to uint32 (the high word of the argmax / sampler keys)."""
+    import numpy as np
+
+    bits = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def penalised_logits_f32(logits_f32, seen, penalty: float):
+    """``seen(j) ? (z < 0 ? z * penalty : z / penalty) : z`` in float32, as the kernels compute it."""
+    import numpy as np
+
+    z = np.ascontiguousarray(logits_f32, dtype=np.float32)
+    th = np.float32(penalty)
+    with np.errstate(all="ignore"):
+        pen = np.where(z < 0, z * th, z / th).astype(np.float32)
+    return np.where(np.asarray(seen, dtype=bool), pen, z).astype(np.float32)
+
+
+def sampling_candidates(l):
+    """Token ids ordered by the key ``(f32_ordered(l_j) << 32) | ~j`` descending (ties: lower id first)."""
+    import numpy as np
+
+    key = (f32_ordered(l).astype(np.uint64) << np.uint64(32)) | (~np.arange(l.size, dtype=np.uint32)).astype(np.uint64)
+    return np.argsort(key, kind="stable")[::-1]
+
+
+def reference_sample(logits_f32, seen, penalty: float, params, stream: int, position: int,
+                     margin: float = 1e-9) -> tuple[int, int, bool]:
+    """One sampled token from the ``vocab`` float32 logits of a row, exactly as ``sample.hip``
+    defines it, in numpy float64 from float32 inputs.  ``seen``: bool [vocab].  Returns
+    ``(token, m, decisive)``: m is the nucleus size; ``decisive`` is False when moving the draw
+    ``u * c_{m-1}`` or the nucleus cut ``top_p * W`` by +-``margin`` * W would change the result."""
+    import numpy as np
+
+    l = penalised_logits_f32(logits_f32, seen, penalty)
+    k = min(int(params.top_k), l.size)
+    order = sampling_candidates(l)[:k]
+    lc = l[order]
+    with np.errstate(all="ignore"):
+        x = (lc - lc[0]).astype(np.float32).astype(np.float64)
+    w = np.exp(x / float(params.temperature))
+    c = np.empty(k, dtype=np.float64)
+    acc = 0.0
+    for i in range(k):  # prefix sums in candidate order, one double add each
+        acc += float(w[i])
+        c[i] = acc
+    W = float(c[-1])
+    d = margin * W
+
+    def nucleus(cut):
+        return int(np.searchsorted(c, cut, side="left")) + 1  # the smallest m with c[m-1] >= cut
+
+    def pick(m, target):
+        return int(np.searchsorted(c[:m], target, side="right"))  # the first i with c[i] > target
+
+    top_p = float(params.top_p)
+    decisive = True
+    if top_p >= 1.0:
+        m = k
+    else:
+        cut = top_p * W
+        m = min(nucleus(cut), k)
+        decisive = min(nucleus(cut - d), k) == m and min(nucleus(cut + d), k) == m
+    u = sampling_uniform(int(params.seed), int(stream), int(position))
+    target = u * float(c[m - 1])
+    i = min(pick(m, target), m - 1)
+    decisive = decisive and min(pick(m, target - d), m - 1) == i and min(pick(m, target + d), m - 1) == i
+    return int(order[i]), m, bool(decisive)
+
+
+@torch.no_grad()
+def teacher_forced_sampling_check(model: GPT2Reference, seq: list[int], prompt_len: int, repetition_penalty: float,
+                                  params, eps: float = 0.05) -> dict:
+    """Oracle for a SAMPLED sequence: one fp32 forward over ``seq`` (teacher forcing); a generated
+    token is a mismatch when the oracle says no sampler within a logit error of ``eps`` could have
+    drawn it -- (a) its penalised oracle logit is more than ``eps`` below the ``top_k``-th largest,
+    or (b) the oracle probability mass (softmax at the temperature over the top-k) of the tokens
+    whose logit beats it by more than ``eps`` is >= ``top_p * exp(2 eps / T)``: those tokens rank
+    above it under any eps-perturbation, and an eps-error scales a softmax ratio by at most
+    exp(2 eps / T), so the nucleus closes before it.
+
+    Returns {"positions", "mismatches": [(i, got, reason, value)]}."""
+    cfg = model.cfg
+    dev = model.device
+    S = len(seq)
+    out = {"positions": 0, "mismatches": []}
+    if S <= prompt_len:
+        return out
+    cache = KVCache.allocate(cfg, 1, S, dtype=model.dtype, device=dev)
+    toks = torch.tensor([seq], device=dev)
+    pos = torch.arange(S, device=dev)[None]
+    hidden = model.forward(toks, pos, cache, torch.zeros(1, dtype=torch.long, device=dev))[0]
+    logits = model.logits(hidden[prompt_len - 1: S - 1]).float()  # row j predicts seq[prompt_len + j]
+    n = logits.shape[0]
+    seen = torch.zeros(n, cfg.vocab_size, dtype=torch.bool, device=dev)
+    for j in range(n):
+        seen[j, torch.tensor(seq[: prompt_len + j], device=dev)] = True
+    logits = apply_repetition_penalty(logits, seen, repetition_penalty).double()
+    k = min(int(params.top_k), cfg.vocab_size)
+    T, top_p = float(params.temperature), float(params.top_p)
+    out["positions"] = n
+    got = torch.tensor(seq[prompt_len:], device=dev)
+    top = logits.topk(k, dim=-1).values  # [n, k], descending
+    lg = logits.gather(1, got[:, None])  # [n, 1]
+    short = (top[:, -1:] - lg)[:, 0]  # how far below the k-th largest
+    p = torch.softmax(top / T, dim=-1)
+    mass = (p * (top > lg + eps)).sum(dim=-1)  # oracle mass of the tokens that beat it by more than eps
+    short, mass = short.tolist(), mass.tolist()
+    for j in range(n):
+        if short[j] > eps:
+            out["mismatches"].append((prompt_len + j, seq[prompt_len + j], "below top-k", short[j]))
+        elif top_p < 1.0 and mass[j] >= top_p * math.exp(2 * eps / T):
+            out["mismatches"].append((prompt_len + j, seq[prompt_len + j], "outside nucleus", mass[j]))
     return out

@@ -27,12 +27,13 @@ LIB_DIR = _HERE / "_lib"
 LIB_PATH = LIB_DIR / "libdlms_hip.so"
 # debug variant: device-side range checks on every data-dependent index (common.h, DLMS_DEVICE_CHECKS)
 CHECKED_LIB_PATH = LIB_DIR / "libdlms_hip_checked.so"
-CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps")
+CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "sample")
 CHECK_SITES = {1: "embed token id", 2: "position id", 3: "decode_update slot_map", 4: "decode_update token id",
                5: "decode_update sequence length", 6: "seen_set row", 7: "QKV scatter slot", 8: "QKV scatter position",
-               9: "attention slot", 10: "BERT token id", 11: "seen_set token id"}
+               9: "attention slot", 10: "BERT token id", 11: "seen_set token id", 12: "sampler slot_map",
+               13: "sampled token id"}
 SOURCES = ["api.hip", "gemm.hip", "norm.hip", "attention.hip", "decode.hip", "encoder.hip", "xgmi.hip", "skinny.hip", "gemm_ps.hip",
-           "dataflow.hip", "mid.hip"]
+           "dataflow.hip", "mid.hip", "sample.hip"]
 ARCH = os.environ.get("DLMS_OFFLOAD_ARCH", "gfx950")
 
 EPI_BF16, EPI_GELU_TANH, EPI_GELU_ERF, EPI_F32, EPI_QKV, EPI_ARGMAX, EPI_PARTIAL = range(7)
@@ -167,6 +168,9 @@ def _bind(L):
         "dlms_mid_proj": [P, I, P, P, P, I, I, I, I, I, P],
         "dlms_gemm_ps": [I, P, I, P, I, I, I, I, I, I, I, ctypes.POINTER(GemmEpi), P],
         "dlms_attention_persist": [P, I, P, P, P, P, P, I, I, I, I, I, F, I, P],
+        "dlms_sample_topk_topp": [P, ctypes.c_longlong, P, I, P, P, P, I, P, F, ctypes.c_double, I, ctypes.c_double, I,
+                                  P, ctypes.c_longlong, I, P],
+        "dlms_philox4x32_10": [P, P, I, P],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -686,7 +690,64 @@ def decode_update(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok,
            "dlms_decode_update")
 
 
-def bert_embed_ln(ids, positions, word, pos_emb, type0, gamma, beta, eps: float, out_f32=None, out_bf16=None):
+SAMPLE_MAX_TOP_K = 256  # sample.hip SMP_MAX_K
+
+
+def sample_topk_topp(logits: torch.Tensor, seen: torch.Tensor, lens: torch.Tensor, streams: torch.Tensor,
+                     seed: torch.Tensor, penalty: float, temperature: float, top_k: int, top_p: float, vocab: int,
+                     keys_out: torch.Tensor, slot_map: torch.Tensor | None = None) -> torch.Tensor:
+    """Seeded temperature / top-k / top-p draw per row of f32 ``logits`` [B, ld] (columns >= ``vocab``
+    ignored) under the repetition penalty of ``seen`` [B, words]: writes one argmax-style key
+    ``(f32_ordered(l_tok) << 32) | ~tok`` per row into ``keys_out[:, 0]`` (int64 [B, >= 1]), which
+    ``decode_update`` consumes.  Row i draws with counter (``lens[s]``, ``streams[s]``) of its slot
+    s = ``slot_map[i]`` (default i) under the device word ``seed`` (int64 [1]).  The definition:
+    ``sample.hip`` / ``models.gpt2.reference_sample``."""
+    _req(logits, torch.float32, "logits", 2)
+    _req(seen, torch.int32, "seen", 2)
+    _req(lens, torch.int32, "lens", 1)
+    _req(streams, torch.int64, "streams", 1)
+    _req(seed, torch.int64, "seed")
+    _req(keys_out, torch.int64, "keys_out", 2)
+    B, ld = logits.shape[0], logits.stride(0)
+    if B < 1 or not 1 <= vocab <= min(logits.shape[1], 65536) or ld % 4 or logits.data_ptr() % 16 or ld > 65536:
+        raise ValueError(f"sample_topk_topp: logits {tuple(logits.shape)} (row stride {ld}) vs vocab {vocab}")
+    if seen.shape[0] < B or seen.shape[1] * 32 < vocab or seen.stride(0) != seen.shape[1]:
+        raise ValueError("sample_topk_topp: seen must be contiguous [>= B, >= vocab / 32] rows")
+    if not (temperature > 0 and temperature < float("inf")) or not 1 <= top_k <= SAMPLE_MAX_TOP_K or \
+            not 0 < top_p <= 1 or not penalty > 0:
+        raise ValueError("sample_topk_topp: temperature > 0, 1 <= top_k <= 256, 0 < top_p <= 1, penalty > 0")
+    if keys_out.shape[0] < B or keys_out.shape[1] < 1 or seed.numel() < 1:
+        raise ValueError("sample_topk_topp: keys_out / seed too small")
+    nslots = B
+    if slot_map is not None:
+        _req(slot_map, torch.int32, "slot_map", 1)
+        if slot_map.numel() < B:
+            raise ValueError("slot_map too short")
+        nslots = lens.numel()  # callers guarantee every slot_map entry is < the state capacity
+    if lens.numel() < nslots or streams.numel() < nslots:
+        raise ValueError("sample_topk_topp: lens / streams too short")
+    _check(lib().dlms_sample_topk_topp(_p(logits), ld, _p(seen), seen.stride(0), _p(lens), _p(streams), _p(slot_map),
+                                       min(lens.numel(), streams.numel()), _p(seed), float(penalty),
+                                       float(temperature), int(top_k), float(top_p), int(vocab), _p(keys_out),
+                                       keys_out.stride(0), B, _stream()), "dlms_sample_topk_topp")
+    return keys_out
+
+
+def philox4x32_10(counters_keys: torch.Tensor) -> torch.Tensor:
+    """The sampler's device Philox4x32-10 on int64 rows [n, 6] of (4 counter words, 2 key words), each a
+    32-bit value: returns the 4 output words per row (int64 [n, 4]); a known-answer test hook."""
+    ck = counters_keys.to(torch.int64)
+    if ck.dim() != 2 or ck.shape[1] != 6 or ck.device.type != "cuda":
+        raise ValueError("philox4x32_10: int [n, 6] GPU tensor")
+    n = ck.shape[0]
+    # 32-bit words carried in int64: their low halves (little endian), packed
+    in32 = ck.contiguous().view(torch.int32).view(n, 6, 2)[:, :, 0].contiguous()
+    out32 = torch.empty(n, 4, dtype=torch.int32, device=ck.device)
+    _check(lib().dlms_philox4x32_10(_p(in32), _p(out32), n, _stream()), "dlms_philox4x32_10")
+    return out32.to(torch.int64) & 0xffffffff
+
+
+def bert_embed_ln(ids,positions, word, pos_emb, type0, gamma, beta, eps: float, out_f32=None, out_bf16=None):
     _req(ids, torch.int32, "ids", 1)
     _req(positions, torch.int32, "positions", 1)
     for t, n in ((word, "word"), (pos_emb, "pos_emb")):

@@ -15,6 +15,7 @@ Per-request latency, batch sizes and tokens/s land in the metrics registry.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import logging
 import os
 import queue
@@ -29,7 +30,7 @@ import torch
 
 from .. import wire
 from ..engine.scheduler import Overloaded
-from ..models.config import GenerationConfig, gpt2_config
+from ..models.config import GenerationConfig, SamplingParams, gpt2_config
 from ..models.gpt2 import init_gpt2_weights, load_safetensors_weights
 from ..tokenizer import GPT2BPE
 from ..utils.config import parse_with_config
@@ -67,6 +68,7 @@ class Batcher:
     def __init__(self, engine, gen: GenerationConfig, max_batch: int = 64, window_ms: float = 2.0):
         self.engine = engine
         self.gen = gen
+        self.batches = 0  # sampling: batch i draws under seed + i (a run is reproducible, its batches differ)
         self.max_batch = max_batch
         self.window = window_ms / 1e3
         self.q: queue.Queue = queue.Queue()
@@ -101,7 +103,14 @@ class Batcher:
     def _run(self, batch: list[_Req]):
         t0 = time.perf_counter()
         try:
-            outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty)
+            sp = self.gen.sampling()
+            if sp is None:
+                outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty)
+            else:
+                sp = dataclasses.replace(sp, seed=(sp.seed + self.batches) % 2 ** 64)
+                self.batches += 1
+                outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty,
+                                            sampling=sp)
         except Exception as e:  # fail the whole batch, keep serving
             log.exception("generation failed")
             for r in batch:
@@ -198,8 +207,10 @@ def make_gate_worker(model: str, weights: str | None, device):
 class TutoringServer:
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_batch: int = 64, window_ms: float = 2.0,
                  max_length: int = 150, repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None,
-                 workers: int = 64, batching: str = "auto", chunk: int = 8, max_queue: int | None = None):
-        self.gen = GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty)
+                 workers: int = 64, batching: str = "auto", chunk: int = 8, max_queue: int | None = None,
+                 sampling=None):
+        """``sampling`` (a ``SamplingParams``, every server class): answers are sampled, not greedy."""
+        self.gen = generation_config(max_length, repetition_penalty, sampling)
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         if batching == "auto":
             batching = "continuous" if hasattr(engine, "admit") else "window"
@@ -209,7 +220,7 @@ class TutoringServer:
             if engine.max_length != max_length:
                 raise ValueError("continuous batching: engine max_length differs from the server's")
             self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                             max_queue=default_max_queue(engine, max_queue))
+                                             max_queue=default_max_queue(engine, max_queue), sampling=sampling)
         else:
             self.batcher = Batcher(engine, self.gen, max_batch=max_batch, window_ms=window_ms)
         self.batching = batching
@@ -306,7 +317,7 @@ class AioTutoringServer(TutoringServer):
 
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_length: int = 150,
                  repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None, chunk: int = 8,
-                 max_queue: int | None = None):
+                 max_queue: int | None = None, sampling=None):
         import asyncio
 
         from ..engine.scheduler import ContinuousBatcher
@@ -315,10 +326,10 @@ class AioTutoringServer(TutoringServer):
             raise ValueError("the aio front end needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty)
+        self.gen = generation_config(max_length, repetition_penalty, sampling)
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                             max_queue=default_max_queue(engine, max_queue))
+                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling)
         self.batching = "continuous"
         self.engine = engine
         self._stopping = threading.Event()
@@ -365,16 +376,16 @@ class PooledTutoringServer(TutoringServer):
     stop() as ``TutoringServer``."""
 
     def __init__(self, engine, pool, max_length: int = 150, repetition_penalty: float = 1.2, chunk: int = 8,
-                 max_queue: int | None = None):
+                 max_queue: int | None = None, sampling=None):
         from ..engine.scheduler import ContinuousBatcher
 
         if not hasattr(engine, "admit"):
             raise ValueError("the front-end pool needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty)
+        self.gen = generation_config(max_length, repetition_penalty, sampling)
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                             max_queue=default_max_queue(engine, max_queue))
+                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling)
         self.batching = "continuous"
         self.engine = engine
         self.pool = pool
@@ -399,7 +410,23 @@ class PooledTutoringServer(TutoringServer):
 EXIT_FATAL = 75  # EX_TEMPFAIL: the supervisor restarts the replica
 
 
-def main(argv=None):
+def generation_config(max_length: int, repetition_penalty: float, sampling=None) -> GenerationConfig:
+    """The servers' ``GenerationConfig``: greedy, or carrying ``sampling``'s fields with ``do_sample`` set."""
+    if sampling is None:
+        return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty)
+    return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty, do_sample=True,
+                            temperature=sampling.temperature, top_k=sampling.top_k, top_p=sampling.top_p,
+                            seed=sampling.seed)
+
+
+def sampling_from_args(args) -> "SamplingParams | None":
+    """``--sample`` with ``--temperature / --top-k / --top-p / --seed`` -> ``SamplingParams`` (None: greedy)."""
+    if not args.sample:
+        return None
+    return SamplingParams(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+
+
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="GPT-2 tutoring server (MI355X HIP engine)")
     ap.add_argument("--port", type=int, default=int(os.environ.get("DLMS_TUTOR_PORT", "50054")))
     ap.add_argument("--host", default="[::]")
@@ -439,7 +466,30 @@ def main(argv=None):
     ap.add_argument("--gate-vocab", default=None, help="BERT vocab.txt for the gate (synthetic if absent)")
     ap.add_argument("--gate-weights", default=None, help="local safetensors for the gate model")
     ap.add_argument("--log-level", default=os.environ.get("DLMS_LOG", "INFO"))
+    ap.add_argument("--sample", action="store_true",
+                    help="sample the answers (temperature / top-k / top-p, seeded) instead of greedy decoding; "
+                         "bf16 weights on one GPU per replica")
+    ap.add_argument("--temperature", type=float, default=0.7)
+    ap.add_argument("--top-k", type=int, default=50)
+    ap.add_argument("--top-p", type=float, default=0.9)
+    ap.add_argument("--seed", type=int, default=0, help="sampling seed (the n-th request of a run draws from stream n)")
+    return ap
+
+
+def main(argv=None):
+    ap = arg_parser()
     args, _ = parse_with_config(ap, argv)
+    try:
+        sampling = sampling_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if sampling is not None:
+        from ..engine.gpt2_engine import sampling_unsupported
+
+        why = sampling_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+        if why:
+            ap.error(f"--sample: {why}")
+    mode = {} if sampling is None else {"sampling": sampling}
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -493,12 +543,12 @@ def main(argv=None):
     if args.warm_batch > 0 and hasattr(eng, "warm_decode_graphs"):
         # (a TP proxy mirrors the call to every rank of its group: the captures' warm-up steps run
         # the group's collectives, engine/tp_serving.py)
-        n, secs = eng.warm_decode_graphs(args.repetition_penalty, args.warm_batch)
+        n, secs = eng.warm_decode_graphs(args.repetition_penalty, args.warm_batch, **mode)
         log.info("captured %d decode graphs (batch buckets <= %d) in %.1f s", n, args.warm_batch, secs)
     tok = GPT2BPE(args.vocab, args.merges, eos_token_id=eng.cfg.eos_token_id)
     if pool is not None and hasattr(eng, "admit"):
         srv = PooledTutoringServer(eng, pool, args.max_length, args.repetition_penalty, chunk=args.chunk,
-                                   max_queue=args.max_queue)
+                                   max_queue=args.max_queue, **mode)
         if args.serve_gate:
             pool.gate_worker = make_gate_worker(args.gate_model, args.gate_weights, getattr(eng, "device", "cpu"))
             pool.gate_worker.attach(srv.batcher)
@@ -510,11 +560,11 @@ def main(argv=None):
         pass
     elif args.frontend == "aio" and args.batching != "window" and hasattr(eng, "admit"):
         srv = AioTutoringServer(eng, args.port, args.host, args.max_length, args.repetition_penalty, tokenizer=tok,
-                                chunk=args.chunk, max_queue=args.max_queue)
+                                chunk=args.chunk, max_queue=args.max_queue, **mode)
     else:
         srv = TutoringServer(eng, args.port, args.host, args.max_batch, args.window_ms, args.max_length,
                              args.repetition_penalty, tokenizer=tok, batching=args.batching, chunk=args.chunk,
-                             max_queue=args.max_queue)
+                             max_queue=args.max_queue, **mode)
     done = threading.Event()
     fatal: list = []
 
