@@ -182,6 +182,17 @@ def sampling_unsupported(tp_size: int, fp8: bool) -> str | None:
     return None
 
 
+def kv_fp8_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
+    """Why an engine of this shape cannot hold an fp8 (e4m3) KV cache (None: it can)."""
+    if tp_size > 1:
+        return ("the fp8 KV cache is not supported with tensor parallelism (tp_size > 1): the TP-fused decode path "
+                "has no fp8-cache build; serve kv_dtype='bf16' or TP=1")
+    if fp8_weights:
+        return ("the fp8 KV cache is not supported with fp8 weights: the W8A8 QKV GEMM has no fp8-cache epilogue; "
+                "serve kv_dtype='bf16' or weight_dtype='bf16'")
+    return None
+
+
 class HipGPT2Engine:
     # (row, head) pairs up to which decode attention uses the split-K kernel (profiles/r2_skinny_bench.log:
     # at 32 rows x 12 heads, T=150: 7.9 us vs 12.3 us for one wave per pair)
@@ -199,8 +210,18 @@ class HipGPT2Engine:
                  max_batch: int | str = 256, max_length: int = 150, tp_group=None, use_graph: bool = True,
                  check_every: int = 16, max_batch_cap: int = 4096, weight_dtype: str = "bf16",
                  overlap: bool | None = None, overlap_min_batch: int = 512, overlap_parts: int | None = None,
-                 p2p: bool | None = None, latency_path: bool | None = None, prefill_split: int | None = None):
-        """``weight_dtype="fp8"``: W8A8 OCP-e4m3 MFMA GEMMs for QKV, c_fc and the LM head (activation
+                 p2p: bool | None = None, latency_path: bool | None = None, prefill_split: int | None = None,
+                 kv_dtype: str = "bf16"):
+        """``kv_dtype="fp8"``: the KV cache holds OCP e4m3 bytes without scales
+        (``models.gpt2.quantize_kv_e4m3``: the bf16 cache's content, saturated and rounded to
+        nearest-even e4m3) -- half the bytes the decode attention streams and twice the slots per
+        GiB, at reduced precision (the oracle is ``GPT2Reference(kv_dtype="fp8")``).  Every batch
+        size then runs the tiled step (QKV GEMM scattering e4m3, the fp8 wave / persistent decode
+        attention, the fp8 tile attention in the prefill): the latency, mid, fused
+        attention-out-projection, fused-MLP and dataflow paths have no fp8-cache build and are off;
+        the overlapped >= 512-row step is on.  Not with ``tp_group`` or ``weight_dtype="fp8"``
+        (out of scope: ``ValueError``).  The bf16 default is the reference-precision cache.
+        ``weight_dtype="fp8"``: W8A8 OCP-e4m3 MFMA GEMMs for QKV, c_fc and the LM head (activation
         rows scaled by the fused LayerNorms); the bf16 default is the reference-precision path.
         ``overlap``: decode batches of >= ``overlap_min_batch`` rows run as ``overlap_parts`` row
         ranges on as many streams (attention of one beside the GEMMs of the others); default from
@@ -219,10 +240,19 @@ class HipGPT2Engine:
         ``prefill_split``: pin the split-K of the prefill's row-parallel projections (default: a
         heuristic of the packed row count) so a prompt's arithmetic does not depend on what else is
         admitted with it -- continuous batching is then bit-identical to serving it alone."""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype {kv_dtype!r}: bf16 or fp8")
+        if kv_dtype == "fp8":
+            w8 = weights.fp8 if isinstance(weights, GPT2DeviceWeights) else weight_dtype == "fp8"
+            why = kv_fp8_unsupported(2 if tp_group is not None else 1, w8)
+            if why:
+                raise ValueError(why)
         if not torch.cuda.is_available():
             raise RuntimeError("HipGPT2Engine needs a GPU (use TorchGPT2Engine on CPU)")
         ops.lib()  # fail loudly if the kernel library is missing
         self.cfg = cfg
+        self.kv_dtype = kv_dtype
+        self.kv_fp8 = kv_dtype == "fp8"
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.index is None:  # pin "cuda" to a concrete ordinal (scheduler threads set it)
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -246,7 +276,7 @@ class HipGPT2Engine:
             from .memory import plan_max_batch
 
             max_batch = plan_max_batch(cfg, max_length, self.tp_size, weights_resident=True, cap=max_batch_cap,
-                                       device=self.device)
+                                       device=self.device, kv_dtype=kv_dtype)
         self.max_batch = int(max_batch)
         self.max_length = max_length
         self.use_graph = use_graph
@@ -304,6 +334,10 @@ class HipGPT2Engine:
             raise ValueError("overlap_parts: 2, 3 or 4 (one hardware queue each)")
         if latency_path is None:
             latency_path = os.environ.get("DLMS_LATENCY_PATH", "1") != "0"
+        if self.kv_fp8:
+            # the latency-shaped kernels (skinny / mid / fused attention + out-projection / fused MLP)
+            # scatter and read a bf16 cache: every batch size runs the tiled step
+            latency_path = False
         # (fp8 engines too: the latency path runs the bf16 weights the fp8 engine keeps beside its e4m3
         # copies -- at <= 8 rows the decode is bound by launch and dependency latency, not weight bytes;
         # W8A8 serves the prefill and the larger batches, where the weight stream matters)
@@ -423,7 +457,7 @@ class HipGPT2Engine:
         # DLMS_DATAFLOW_ROWS (1 or 2) the row counts it serves, DLMS_DATAFLOW=0 turns it off.
         df_env = os.environ.get("DLMS_DATAFLOW", "auto")
         self.dataflow_rows = max(1, min(2, int(os.environ.get("DLMS_DATAFLOW_ROWS", "1"))))
-        self.dataflow = (df_env != "0" and tp_group is None and not self.w.fp8 and
+        self.dataflow = (df_env != "0" and tp_group is None and not self.w.fp8 and not self.kv_fp8 and
                          (df_env == "1" or cfg.n_embd in (768, 1024)) and self._df_supported())
         self._df = None
         self._df_status = None  # the last decode() launch's error words in flight (dataflow_status_async)
@@ -461,7 +495,8 @@ class HipGPT2Engine:
         T = self.max_length
         i32, f32, bf = torch.int32, torch.float32, torch.bfloat16
         # KV cache [L][2][slots][H_local][T][64]: sized for the batch at full length.
-        self.kv = torch.zeros(cfg.n_layer, 2, B, Hl, T, 64, dtype=bf, device=dev)
+        # (kv_dtype="fp8": the same shape in e4m3 bytes, 64-B key rows; zero bytes are +0.0)
+        self.kv = torch.zeros(cfg.n_layer, 2, B, Hl, T, 64, dtype=ops.FP8 if self.kv_fp8 else bf, device=dev)
         self.x = torch.zeros(B, D, dtype=f32, device=dev)
         # second residual buffer: the latency path's fused add+LN kernels advance x by ping-pong
         self.x2 = torch.zeros(min(B, 64), D, dtype=f32, device=dev)
@@ -635,7 +670,7 @@ class HipGPT2Engine:
             return
         if r.tiles is not None:  # packed prompts (K6): 16-query MFMA tiles
             ops.tile_attention(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, r.tiles, out=r.att)
-        elif r.M * self.w.n_heads_local <= self.SPLIT_ATTN_MAX_PAIRS:
+        elif r.M * self.w.n_heads_local <= self.SPLIT_ATTN_MAX_PAIRS and not self.kv_fp8:
             # decode with few (row, head) pairs: split-K flash-decode puts NW waves on each pair's keys
             nw, ns = ops.attention_split_geometry(r.M * self.w.n_heads_local, self.max_length)
             ops.attention_split(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, out=r.att,
@@ -1610,12 +1645,15 @@ class TorchGPT2Engine:
     """CPU (or any-device) engine on the plain-torch reference model: BASELINE config 1."""
 
     def __init__(self, cfg: GPT2Config, weights: dict[str, torch.Tensor], device="cpu", max_length: int = 150,
-                 dtype=torch.float32):
+                 dtype=torch.float32, kv_dtype: str = "bf16"):
+        """``kv_dtype="fp8"``: the reference model of the fp8 (e4m3) KV cache
+        (``GPT2Reference(kv_dtype="fp8")``)."""
         from ..models.gpt2 import GPT2Reference
 
         self.cfg = cfg
         self.max_length = max_length
-        self.model = GPT2Reference(cfg, weights, device=device, dtype=dtype)
+        self.kv_dtype = kv_dtype
+        self.model = GPT2Reference(cfg, weights, device=device, dtype=dtype, kv_dtype=kv_dtype)
 
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,

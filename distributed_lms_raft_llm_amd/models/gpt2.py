@@ -93,11 +93,25 @@ class KVCache:
 class GPT2Reference:
     """Plain-torch GPT-2 forward with a KV cache (batch, ragged prompt lengths)."""
 
-    def __init__(self, cfg: GPT2Config, weights: dict[str, torch.Tensor], device="cpu", dtype=torch.float32):
+    def __init__(self, cfg: GPT2Config, weights: dict[str, torch.Tensor], device="cpu", dtype=torch.float32,
+                 kv_dtype: str = "bf16", act_dtype=None):
+        """``kv_dtype="fp8"``: the model of the engines' fp8 KV cache -- k and v pass through
+        ``quantize_kv_e4m3`` (and back to ``dtype``) where they are written into the cache, so every
+        attention read sees the quantised values.  The default writes them as they are (the fp32
+        oracle of the bf16-cache engines).
+        ``act_dtype`` (measurement only, ``kv_fp8_margin``): round the activations a bf16 engine
+        rounds (LN outputs, q, attention output, GELU output, final hidden) to that dtype."""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype {kv_dtype!r}: bf16 or fp8")
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
+        self.kv_dtype = kv_dtype
+        self.act_dtype = act_dtype
         self.w = {k: v.to(device=self.device, dtype=dtype) for k, v in weights.items()}
+
+    def _act(self, t: torch.Tensor) -> torch.Tensor:
+        return t if self.act_dtype is None else t.to(self.act_dtype).to(t.dtype)
 
     def _ln(self, x, name):
         return torch.nn.functional.layer_norm(
@@ -120,12 +134,17 @@ class GPT2Reference:
         bidx = rows[:, None].expand(B, S)
         for i in range(cfg.n_layer):
             p = f"transformer.h.{i}."
-            h = self._ln(x, p + "ln_1")
+            h = self._act(self._ln(x, p + "ln_1"))
             qkv = h @ self.w[p + "attn.c_attn.weight"] + self.w[p + "attn.c_attn.bias"]
             q, k, v = qkv.split(d, dim=-1)
-            q = q.view(B, S, H, hd)
+            q = self._act(q).view(B, S, H, hd)
             k = k.view(B, S, H, hd)
             v = v.view(B, S, H, hd)
+            if self.kv_dtype == "fp8":
+                k = quantize_kv_e4m3(k).to(x.dtype)
+                v = quantize_kv_e4m3(v).to(x.dtype)
+            elif self.act_dtype is not None:  # (measurement only) the bf16 cache of a bf16 engine
+                k, v = self._act(k), self._act(v)
             cache.data[i, 0, bidx, :, positions] = k.to(cache.data.dtype)
             cache.data[i, 1, bidx, :, positions] = v.to(cache.data.dtype)
             K = cache.data[i, 0, rows].to(x.dtype)  # [B, H, Tmax, hd]
@@ -133,12 +152,12 @@ class GPT2Reference:
             att = torch.einsum("bshd,bhtd->bhst", q, K) / math.sqrt(hd)
             att = att.masked_fill(~mask[:, None, :, :], float("-inf"))
             att = torch.softmax(att, dim=-1)
-            a = torch.einsum("bhst,bhtd->bshd", att, V).reshape(B, S, d)
+            a = self._act(torch.einsum("bhst,bhtd->bshd", att, V).reshape(B, S, d))
             x = x + a @ self.w[p + "attn.c_proj.weight"] + self.w[p + "attn.c_proj.bias"]
-            h = self._ln(x, p + "ln_2")
-            f = gelu_new(h @ self.w[p + "mlp.c_fc.weight"] + self.w[p + "mlp.c_fc.bias"])
+            h = self._act(self._ln(x, p + "ln_2"))
+            f = self._act(gelu_new(h @ self.w[p + "mlp.c_fc.weight"] + self.w[p + "mlp.c_fc.bias"]))
             x = x + f @ self.w[p + "mlp.c_proj.weight"] + self.w[p + "mlp.c_proj.bias"]
-        return self._ln(x, "transformer.ln_f")
+        return self._act(self._ln(x, "transformer.ln_f"))
 
     def logits(self, hidden: torch.Tensor) -> torch.Tensor:
         return hidden @ self.w["transformer.wte.weight"].t()
@@ -294,6 +313,71 @@ def teacher_forced_check_batch(model: GPT2Reference, seqs: list[list[int]], prom
                     if s[pl + j] != want[j]:
                         r["mismatches"].append((pl + j, s[pl + j], want[j], margin[j]))
             out.append(r)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# fp8 KV cache: the normative CPU definition of what the engines' e4m3 cache holds
+# ---------------------------------------------------------------------------------------------
+KV_E4M3_MAX = 448.0  # largest finite OCP e4m3fn value
+
+
+def quantize_kv_e4m3(x: torch.Tensor) -> torch.Tensor:
+    """The fp8 KV cache's content for the K / V values ``x`` (bias included, any float dtype):
+    ``e4m3_rne(clamp(bf16_rne(x), -448, 448))`` as a ``torch.float8_e4m3fn`` tensor -- the bf16
+    cache's content, saturated and rounded to nearest-even OCP e4m3, without scales.  The bf16
+    rounding comes first (double rounding is part of the definition: the kernels quantise the
+    bf16 values the bf16 cache would hold); the clamp keeps the result independent of a
+    conversion's overflow behaviour and the NaN byte (0x7F / 0xFF) out of the cache.
+    Dequantisation (``.float()`` / ``.to(bf16)``) is exact."""
+    return x.to(torch.bfloat16).float().clamp(-KV_E4M3_MAX, KV_E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+@torch.no_grad()
+def kv_fp8_margin(cfg: GPT2Config, weights: dict[str, torch.Tensor], prompts: list[list[int]], max_length: int,
+                  repetition_penalty: float = 1.2, base_eps: float = 0.05) -> dict:
+    """Derive, from the reference alone, the teacher-forced margin ``eps`` that an fp8-cache engine
+    is held to.  An engine's K / V differ from the fp32 oracle's by bf16-arithmetic noise ahead of
+    the quantiser; on the e4m3 grid that noise now and then flips a rounding by a whole step, so
+    the logits deviate more than with a bf16 cache.  For each cache type the reference is
+    evaluated teacher-forced on its own greedy generations twice -- exactly, and with the
+    activations a bf16 engine rounds (LN outputs, q, attention output, GELU output, final hidden;
+    for the bf16 cache also k and v) rounded to bf16 -- and the largest logit difference over the
+    generated positions is taken.  ``eps`` = ``base_eps`` scaled by the ratio fp8 / bf16.
+
+    Returns {"dev_fp8", "dev_bf16", "ratio", "eps", "positions", "decisive_share"(eps)}: the last
+    is a function giving the share of the fp8 reference's positions that stay decisive at eps."""
+    out: dict = {}
+    margins: list[float] = []
+    for kv in ("fp8", "bf16"):
+        exact = GPT2Reference(cfg, weights, kv_dtype=kv)
+        noisy = GPT2Reference(cfg, weights, kv_dtype=kv, act_dtype=torch.bfloat16)
+        seqs = reference_generate(exact, prompts, max_length=max_length, repetition_penalty=repetition_penalty)
+        dev, npos = 0.0, 0
+        for s, p in zip(seqs, prompts):
+            S, pl = len(s), len(p)
+            if S <= pl:
+                continue
+            toks = torch.tensor([s])
+            pos = torch.arange(S)[None]
+            row = torch.zeros(1, dtype=torch.long)
+            lg = []
+            for m in (exact, noisy):
+                cache = KVCache.allocate(cfg, 1, S, dtype=m.dtype)
+                lg.append(m.logits(m.forward(toks, pos, cache, row)[0][pl - 1: S - 1]))
+            dev = max(dev, float((lg[0] - lg[1]).abs().max()))
+            npos += S - pl
+            if kv == "fp8":
+                seen = torch.zeros(S - pl, cfg.vocab_size, dtype=torch.bool)
+                for j in range(S - pl):
+                    seen[j, torch.tensor(s[: pl + j])] = True
+                top = apply_repetition_penalty(lg[0], seen, repetition_penalty).topk(2, dim=-1).values
+                margins += (top[:, 0] - top[:, 1]).tolist()
+        out["dev_" + kv] = dev
+        out["positions"] = npos
+    out["ratio"] = out["dev_fp8"] / out["dev_bf16"]
+    out["eps"] = base_eps * out["ratio"]
+    out["decisive_share"] = lambda eps: sum(m > eps for m in margins) / max(1, len(margins))
     return out
 
 

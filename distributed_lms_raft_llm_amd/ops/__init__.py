@@ -119,6 +119,7 @@ class GemmEpi(ctypes.Structure):
         ("split_k", ctypes.c_int), ("split_stride", ctypes.c_longlong),
         ("a_scale", ctypes.c_void_p), ("w_scale", ctypes.c_void_p),
         ("n_slots", ctypes.c_int),
+        ("kv_fp8", ctypes.c_int),
     ]
 
 
@@ -143,6 +144,9 @@ def _bind(L):
         "dlms_row_attention": [P, I, P, P, P, P, P, I, I, I, I, I, F, P],
         "dlms_attention": [P, I, P, P, P, P, P, I, I, I, I, I, F, P],
         "dlms_tile_attention": [P, I, P, P, P, P, P, I, P, I, I, I, I, F, P],
+        "dlms_attention_fp8": [P, I, P, P, P, P, P, I, I, I, I, I, F, P],
+        "dlms_attention_persist_fp8": [P, I, P, P, P, P, P, I, I, I, I, I, F, I, P],
+        "dlms_tile_attention_fp8": [P, I, P, P, P, P, P, I, P, I, I, I, I, F, P],
         "dlms_embed": [P, P, P, P, P, I, I, I, I, I, P],
         "dlms_decode_update": [P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, I, P, I, P, P, P, P, P, P, I, I,
                                I, I, I, I, I, P, P, F, P, I, P],
@@ -298,6 +302,22 @@ def _req(t: torch.Tensor, dtype, name: str, dim: int | None = None):
         raise ValueError(f"{name}: last dim must be contiguous")
 
 
+def _kv_dtype(k_cache: torch.Tensor, v_cache: torch.Tensor, what: str, fp8_ok: bool = True) -> bool:
+    """The KV cache's element type, from the cache tensors: bf16 (False) or the fp8 cache (True:
+    ``FP8`` bytes, 64-B key rows, no scales).  ``ValueError`` for mixed K / V dtypes and for a path
+    that has no fp8-cache build (``fp8_ok`` False)."""
+    if not isinstance(k_cache, torch.Tensor) or not isinstance(v_cache, torch.Tensor):
+        raise TypeError(f"{what}: k_cache and v_cache must be tensors")
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"{what}: k_cache is {k_cache.dtype}, v_cache is {v_cache.dtype}: one cache dtype")
+    if k_cache.dtype == FP8:
+        if not fp8_ok:
+            raise ValueError(f"{what}: no fp8 KV-cache build of this path (the tiled QKV GEMM on bf16 weights, "
+                             f"the wave / persistent decode attention and the tile attention have one)")
+        return True
+    return False
+
+
 # ---------------------------------------------------------------------------------------------
 # GEMM
 # ---------------------------------------------------------------------------------------------
@@ -342,8 +362,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epi: int = EPI_BF16, *, bias=None, ou
                 raise ValueError("resid too small")
             ep.resid, ep.ldr = resid.data_ptr(), resid.stride(0)
     elif epi == EPI_QKV:
-        for t, n in ((q_out, "q_out"), (k_cache, "k_cache"), (v_cache, "v_cache")):
-            _req(t, torch.bfloat16, n)
+        kv8 = _kv_dtype(k_cache, v_cache, "gemm(EPI_QKV)", fp8_ok=not fp8)
+        _req(q_out, torch.bfloat16, "q_out")
+        for t, n in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+            _req(t, FP8 if kv8 else torch.bfloat16, n)
+            if kv8 and not t.is_contiguous():
+                raise ValueError(f"gemm(EPI_QKV): the fp8 {n} must be contiguous")
+        ep.kv_fp8 = int(kv8)
         _req(row_slot, torch.int32, "row_slot", 1)
         _req(row_pos, torch.int32, "row_pos", 1)
         if N % 3:
@@ -515,20 +540,35 @@ def row_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
     impl "wave": one wave per (row, head), online softmax (default); "lds": block per (row, head),
     exact two-pass softmax through LDS (t_max <= 2048)."""
     _req(q, torch.bfloat16, "q", 2)
-    _req(k_cache, torch.bfloat16, "k_cache", 4)
-    _req(v_cache, torch.bfloat16, "v_cache", 4)
+    kv8 = _kv_dtype(k_cache, v_cache, f"row_attention(impl={impl!r})", fp8_ok=impl in ("wave", "persist"))
+    _req(k_cache, FP8 if kv8 else torch.bfloat16, "k_cache", 4)
+    _req(v_cache, FP8 if kv8 else torch.bfloat16, "v_cache", 4)
     _req(row_slot, torch.int32, "row_slot", 1)
     _req(row_kvlen, torch.int32, "row_kvlen", 1)
     R = q.shape[0]
     S, H, T, hd = k_cache.shape
     if hd != 64 or v_cache.shape != k_cache.shape or q.shape[1] < H * 64 or T > 2048:
         raise ValueError("row_attention: bad shapes")
+    if kv8 and (not k_cache.is_contiguous() or not v_cache.is_contiguous() or k_cache.data_ptr() % 16 or
+                v_cache.data_ptr() % 16 or q.stride(0) % 8 or q.data_ptr() % 16):
+        raise ValueError("row_attention: the fp8 caches must be contiguous and 16-byte aligned, like q's rows")
     if row_slot.numel() < R or row_kvlen.numel() < R:
         raise ValueError("row_attention: index arrays too short")
     if out is None:
         out = torch.empty(R, H * 64, dtype=torch.bfloat16, device=q.device)
     _req(out, torch.bfloat16, "out", 2)
     sc = (1.0 / 8.0) if scale is None else scale
+    if kv8 and (out.stride(0) % 8 or out.data_ptr() % 16):
+        raise ValueError("row_attention: out rows must be 16-byte aligned")
+    if kv8 and impl == "wave":
+        _check(lib().dlms_attention_fp8(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen),
+                                        _p(out), out.stride(0), R, H, T, S, float(sc), _stream()), "attention_fp8")
+        return out
+    if kv8:  # impl == "persist"
+        _check(lib().dlms_attention_persist_fp8(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot),
+                                                _p(row_kvlen), _p(out), out.stride(0), R, H, T, S, float(sc),
+                                                int(blocks), _stream()), "attention_persist_fp8")
+        return out
     if impl == "persist":  # fixed low-occupancy grid looping over (row, head) pairs
         _check(lib().dlms_attention_persist(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen),
                                             _p(out), out.stride(0), R, H, T, S, float(sc), int(blocks), _stream()),
@@ -571,14 +611,17 @@ def tile_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     (row r attends keys [0, row_kvlen[r]) of slot row_slot[r]); every tile's rows belong to one
     sequence (``AttnTiles`` builds them from the packed sequence lengths)."""
     _req(q, torch.bfloat16, "q", 2)
-    _req(k_cache, torch.bfloat16, "k_cache", 4)
-    _req(v_cache, torch.bfloat16, "v_cache", 4)
+    kv8 = _kv_dtype(k_cache, v_cache, "tile_attention")
+    _req(k_cache, FP8 if kv8 else torch.bfloat16, "k_cache", 4)
+    _req(v_cache, FP8 if kv8 else torch.bfloat16, "v_cache", 4)
     _req(row_slot, torch.int32, "row_slot", 1)
     _req(row_kvlen, torch.int32, "row_kvlen", 1)
     R = q.shape[0]
     S, H, T, hd = k_cache.shape
     if hd != 64 or v_cache.shape != k_cache.shape or q.shape[1] < H * 64:
         raise ValueError("tile_attention: bad shapes")
+    if kv8 and (k_cache.data_ptr() % 8 or v_cache.data_ptr() % 8):
+        raise ValueError("tile_attention: the fp8 caches must be 8-byte aligned")
     if not k_cache.is_contiguous() or not v_cache.is_contiguous():
         raise ValueError("tile_attention: caches must be contiguous")
     if tiles.rows > R or row_slot.numel() < tiles.rows or row_kvlen.numel() < tiles.rows:
@@ -589,9 +632,9 @@ def tile_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     if out.shape[0] < tiles.rows or q.stride(0) % 8 or out.stride(0) % 8 or q.data_ptr() % 16 or out.data_ptr() % 16:
         raise ValueError("tile_attention: rows must be 16-byte aligned")
     sc = (1.0 / 8.0) if scale is None else scale
-    _check(lib().dlms_tile_attention(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen),
-                                     _p(tiles.t), tiles.n, _p(out), out.stride(0), H, T, k_cache.shape[0], float(sc),
-                                     _stream()),
+    fn = lib().dlms_tile_attention_fp8 if kv8 else lib().dlms_tile_attention
+    _check(fn(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), _p(tiles.t), tiles.n, _p(out),
+              out.stride(0), H, T, k_cache.shape[0], float(sc), _stream()),
            "tile_attention")
     return out
 

@@ -334,6 +334,240 @@ __global__ __launch_bounds__(256) void attn_persist_kernel(const bf16_t* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Decode attention over the fp8 (OCP e4m3, no scales) KV cache: [slots][H][t_max][64] BYTES, one
+// contiguous 64-B row per key.  Lane (g = lane>>2, c = lane&3) owns dims [16c, 16c+16) of keys
+// t = 16i + g: every lane still issues 16-B loads and a wave-instruction reads 16 whole key rows
+// (1 KiB contiguous).  A score is summed over the 4 lanes of a key (two quad DPP steps instead of
+// group8_sum), the bytes are widened with the packed fp8 -> f32 conversions (exact), and q, the
+// online softmax and the accumulation are those of the bf16 kernels.  Half the bytes per key: the
+// same unroll depth keeps the same bytes, hence twice the keys, in flight per wave.
+__device__ __forceinline__ float group4_sum(float s) {
+    s += dpp_perm<0xB1>(s);
+    s += dpp_perm<0x4E>(s);
+    return s;
+}
+
+__device__ __forceinline__ uint4 kv8_load_nt(const unsigned char* p) {
+    const u32x4_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+    return make_uint4(a.x, a.y, a.z, a.w);
+}
+
+// q dims [16c, 16c+16) of one (row, head), scaled
+__device__ __forceinline__ void kv8_load_q(const bf16_t* qp, float scale_log2, float* qf) {
+    unpack8(*reinterpret_cast<const uint4*>(qp), qf);
+    unpack8(*reinterpret_cast<const uint4*>(qp + 8), qf + 8);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) qf[j] *= scale_log2;
+}
+
+__device__ __forceinline__ float kv8_dot(const float* qf, const uint4 kr) {
+    float kf[16];
+    unpack16_e4m3(kr, kf);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += qf[j] * kf[j];
+    return group4_sum(s);
+}
+
+// merge the 16 key groups (lanes c, c+4, ..., c+60 hold partials of the same dims) and store
+__device__ __forceinline__ void kv8_merge_store(float m, float l, float* acc, int g, bf16_t* op) {
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {
+        float mx, my, lx, ly;  // (own, partner) or (lower, upper): the merge is symmetric
+        lane_pair(m, o, mx, my);
+        lane_pair(l, o, lx, ly);
+        const float m_n = fmaxf(mx, my);
+        const float a = mx == -INFINITY ? 0.f : exp2f(mx - m_n);
+        const float b = my == -INFINITY ? 0.f : exp2f(my - m_n);
+        l = lx * a + ly * b;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            float ax, ay;
+            lane_pair(acc[j], o, ax, ay);
+            acc[j] = ax * a + ay * b;
+        }
+        m = m_n;
+    }
+    if (g == 0) {
+        const float inv = 1.f / l;
+        float o16[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) o16[j] = acc[j] * inv;
+        *reinterpret_cast<uint4*>(op) = pack8(o16);
+        *reinterpret_cast<uint4*>(op + 8) = pack8(o16 + 8);
+    }
+}
+
+template <int ATT_UNROLL>
+__global__ __launch_bounds__(256) void attn_wave_fp8_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                            const unsigned char* __restrict__ kc,
+                                                            const unsigned char* __restrict__ vc,
+                                                            const int* __restrict__ row_slot,
+                                                            const int* __restrict__ row_kvlen, bf16_t* out, int ldo,
+                                                            int H, int t_max, int n_slots, float scale_log2) {
+    const int lane = threadIdx.x & 63;
+    const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r = blockIdx.y;
+    if (h >= H) return;
+    const int g = lane >> 2;
+    const int c = lane & 3;
+    const int slot = (int)dlms_idx(row_slot[r], n_slots, CHK_ATTN_SLOT);
+    int kvlen = row_kvlen[r];
+    kvlen = kvlen < 1 ? 1 : (kvlen > t_max ? t_max : kvlen);
+    const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
+    const unsigned char* K = kc + head_off + c * 16;
+    const unsigned char* V = vc + head_off + c * 16;
+
+    float qf[16];
+    kv8_load_q(q + (size_t)r * ldq + h * 64 + c * 16, scale_log2, qf);
+
+    float m = -INFINITY, l = 0.f;
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    for (int t0 = 0; t0 < kvlen; t0 += 16 * ATT_UNROLL) {
+        uint4 kr[ATT_UNROLL], vr[ATT_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ATT_UNROLL; ++u) {
+            int t = t0 + u * 16 + g;
+            t = t < kvlen ? t : kvlen - 1;  // clamped (masked below): loads never leave the slot
+            kr[u] = kv8_load_nt(K + (size_t)t * 64);
+            vr[u] = kv8_load_nt(V + (size_t)t * 64);
+        }
+#pragma unroll
+        for (int u = 0; u < ATT_UNROLL; ++u) {
+            const float s = kv8_dot(qf, kr[u]);
+            if (t0 + u * 16 + g < kvlen) {
+                const float m_new = fmaxf(m, s);
+                const float corr = exp2f(m - m_new);  // m == -inf -> 0 (acc and l are 0 then)
+                const float p = exp2f(s - m_new);
+                float vf[16];
+                unpack16_e4m3(vr[u], vf);
+                l = l * corr + p;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] = acc[j] * corr + p * vf[j];
+                m = m_new;
+            }
+        }
+    }
+    kv8_merge_store(m, l, acc, g, out + (size_t)r * ldo + h * 64 + c * 16);
+}
+
+// The persistent low-occupancy grid of attn_persist_kernel on the fp8 cache, block-wise rescale
+// (one max, one correction and one acc pass per block of 16 * U keys).  U is chosen by the launcher
+// (dlms_attention_persist_fp8: 4 by default).
+template <int U>
+__global__ __launch_bounds__(256) void attn_persist_fp8_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                               const unsigned char* __restrict__ kc,
+                                                               const unsigned char* __restrict__ vc,
+                                                               const int* __restrict__ row_slot,
+                                                               const int* __restrict__ row_kvlen, bf16_t* out,
+                                                               int ldo, int R, int H, int t_max, int n_slots,
+                                                               float scale_log2) {
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 2;
+    const int c = lane & 3;
+    const int nwaves = gridDim.x * 4;
+    const int npairs = R * H;
+    for (int pair = blockIdx.x * 4 + (threadIdx.x >> 6); pair < npairs; pair += nwaves) {
+        const int r = pair / H, h = pair - r * H;
+        const int slot = (int)dlms_idx(row_slot[r], n_slots, CHK_ATTN_SLOT);
+        int kvlen = row_kvlen[r];
+        kvlen = kvlen < 1 ? 1 : (kvlen > t_max ? t_max : kvlen);
+        const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
+        const unsigned char* K = kc + head_off + c * 16;
+        const unsigned char* V = vc + head_off + c * 16;
+        float qf[16];
+        kv8_load_q(q + (size_t)r * ldq + h * 64 + c * 16, scale_log2, qf);
+        float m = -INFINITY, l = 0.f;
+        float acc[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+        for (int t0 = 0; t0 < kvlen; t0 += 16 * U) {
+            uint4 kr[U], vr[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                int t = t0 + u * 16 + g;
+                t = t < kvlen ? t : kvlen - 1;
+                kr[u] = kv8_load_nt(K + (size_t)t * 64);
+                vr[u] = kv8_load_nt(V + (size_t)t * 64);
+            }
+            float sv[U];
+            float mb = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float s = kv8_dot(qf, kr[u]);
+                sv[u] = t0 + u * 16 + g < kvlen ? s : -INFINITY;
+                mb = fmaxf(mb, sv[u]);
+            }
+            if (mb != -INFINITY) {  // else every key of this lane group is past kvlen
+                const float m_new = fmaxf(m, mb);
+                const float corr = exp2f(m - m_new);  // m == -inf -> 0
+                float ps = 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] *= corr;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float p = exp2f(sv[u] - m_new);  // masked keys -> 0
+                    float vf[16];
+                    unpack16_e4m3(vr[u], vf);
+                    ps += p;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) acc[j] += p * vf[j];
+                }
+                l = l * corr + ps;
+                m = m_new;
+            }
+        }
+        kv8_merge_store(m, l, acc, g, out + (size_t)r * ldo + h * 64 + c * 16);
+    }
+}
+
+extern "C" hipError_t dlms_attention_persist_fp8(const void* q, int ldq, const void* kc, const void* vc,
+                                                 const int* row_slot, const int* row_kvlen, void* out, int ldo,
+                                                 int R, int H, int t_max, int n_slots, float scale, int blocks,
+                                                 hipStream_t stream) {
+    if (R <= 0 || H <= 0 || t_max <= 0 || blocks <= 0) return hipErrorInvalidValue;
+    const int need = (R * H + 3) / 4;
+    // Keys per block = 16 * unroll.  4 (64 keys, 4 KiB of K per wave and block, ~48 KiB per CU with the
+    // 768-workgroup grid) is the measured best in the overlapped step: decode per 1024-query
+    // generation 122.5 ms against 127.2 (6) and 128.1 (8), 512 queries 87.9 / 90.2 / 92.9; alone at
+    // 512 rows x 12 heads, kvlen 150: 24.7 / 23.4 / 32.4 us -- at 150 keys a 128-key block issues its
+    // second block's 16 loads for 22 valid keys (profiles/r10_kv_fp8_unroll_sweep.jsonl).
+    // DLMS_ATTN_FP8_UNROLL = 4 | 6 | 8 overrides (A/B).
+    static int unroll = 0;
+    if (!unroll) {
+        const char* e = getenv("DLMS_ATTN_FP8_UNROLL");
+        const int v = e ? atoi(e) : 0;
+        unroll = (v == 4 || v == 6 || v == 8) ? v : 4;
+    }
+#define DLMS_PERSIST_FP8(U)                                                                                       \
+    hipLaunchKernelGGL((attn_persist_fp8_kernel<U>), dim3(blocks < need ? blocks : need), dim3(256), 0, stream,   \
+                       reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const unsigned char*>(kc),       \
+                       reinterpret_cast<const unsigned char*>(vc), row_slot, row_kvlen,                           \
+                       reinterpret_cast<bf16_t*>(out), ldo, R, H, t_max, n_slots, scale * 1.4426950408889634f)
+    if (unroll == 4)
+        DLMS_PERSIST_FP8(4);
+    else if (unroll == 6)
+        DLMS_PERSIST_FP8(6);
+    else
+        DLMS_PERSIST_FP8(8);
+#undef DLMS_PERSIST_FP8
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_attention_fp8(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
+                                         const int* row_kvlen, void* out, int ldo, int R, int H, int t_max,
+                                         int n_slots, float scale, hipStream_t stream) {
+    if (R <= 0 || H <= 0 || t_max <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_wave_fp8_kernel<4>), dim3((H + 3) / 4, R), dim3(256), 0, stream,
+                       reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const unsigned char*>(kc),
+                       reinterpret_cast<const unsigned char*>(vc), row_slot, row_kvlen,
+                       reinterpret_cast<bf16_t*>(out), ldo, H, t_max, n_slots, scale * 1.4426950408889634f);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t dlms_attention_persist(const void* q, int ldq, const void* kc, const void* vc,
                                              const int* row_slot, const int* row_kvlen, void* out, int ldo, int R,
                                              int H, int t_max, int n_slots, float scale, int blocks,
@@ -396,6 +630,10 @@ extern "C" hipError_t dlms_row_attention(const void* q, int ldq, const void* kc,
 typedef short tr4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) tr4_t lds_tr4_t;
 
+// KV8: the cache is the fp8 byte cache (64-B key rows).  The K chunks and the V rows are loaded as
+// 8-byte pieces and widened to bf16 (exact) before they enter the same fragments / LDS tile; the
+// MFMA part is unchanged.
+template <bool KV8>
 __global__ __launch_bounds__(256) void attn_tile_kernel(const bf16_t* __restrict__ q, int ldq,
                                                         const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
                                                         const int* __restrict__ row_slot,
@@ -444,7 +682,11 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(const bf16_t* __restrict
         for (int i = 0; i < 4; ++i) {
             int key = t0 + (lane >> 3) + 8 * i;
             key = key < kv_end ? key : kv_end - 1;
-            vrow[i] = *reinterpret_cast<const uint4*>(V + (size_t)key * 64 + (lane & 7) * 8);
+            if constexpr (KV8)
+                vrow[i] = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(
+                    reinterpret_cast<const unsigned char*>(vc) + head_off + (size_t)key * 64 + (lane & 7) * 8));
+            else
+                vrow[i] = *reinterpret_cast<const uint4*>(V + (size_t)key * 64 + (lane & 7) * 8);
         }
         // ---- S^T = K . Q^T (two 16-key tiles) ----
         f32x4_t s[2];
@@ -452,8 +694,15 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(const bf16_t* __restrict
         for (int tt = 0; tt < 2; ++tt) {
             int key = t0 + 16 * tt + qi;
             key = key < kv_end ? key : kv_end - 1;
-            const bf16x8_t k0 = *reinterpret_cast<const bf16x8_t*>(K + (size_t)key * 64 + 8 * g);
-            const bf16x8_t k1 = *reinterpret_cast<const bf16x8_t*>(K + (size_t)key * 64 + 32 + 8 * g);
+            bf16x8_t k0, k1;
+            if constexpr (KV8) {
+                const unsigned char* kb = reinterpret_cast<const unsigned char*>(kc) + head_off + (size_t)key * 64;
+                k0 = __builtin_bit_cast(bf16x8_t, e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(kb + 8 * g)));
+                k1 = __builtin_bit_cast(bf16x8_t, e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(kb + 32 + 8 * g)));
+            } else {
+                k0 = *reinterpret_cast<const bf16x8_t*>(K + (size_t)key * 64 + 8 * g);
+                k1 = *reinterpret_cast<const bf16x8_t*>(K + (size_t)key * 64 + 32 + 8 * g);
+            }
             s[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[0], (f32x4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             s[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[1], s[tt], 0, 0, 0);
         }
@@ -535,7 +784,20 @@ extern "C" hipError_t dlms_tile_attention(const void* q, int ldq, const void* kc
                                           int t_max, int n_slots, float scale, hipStream_t stream) {
     if (ntiles <= 0 || H <= 0 || t_max <= 0) return hipErrorInvalidValue;
     const float scale_log2 = scale * 1.4426950408889634f;
-    hipLaunchKernelGGL(attn_tile_kernel, dim3(ntiles, (H + 3) / 4), dim3(256), 0, stream,
+    hipLaunchKernelGGL(attn_tile_kernel<false>, dim3(ntiles, (H + 3) / 4), dim3(256), 0, stream,
+                       reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const bf16_t*>(kc),
+                       reinterpret_cast<const bf16_t*>(vc), row_slot, row_kvlen, tiles, reinterpret_cast<bf16_t*>(out),
+                       ldo, H, t_max, n_slots, scale_log2);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_tile_attention_fp8(const void* q, int ldq, const void* kc, const void* vc,
+                                              const int* row_slot, const int* row_kvlen, const int* tiles, int ntiles,
+                                              void* out, int ldo, int H, int t_max, int n_slots, float scale,
+                                              hipStream_t stream) {
+    if (ntiles <= 0 || H <= 0 || t_max <= 0) return hipErrorInvalidValue;
+    const float scale_log2 = scale * 1.4426950408889634f;
+    hipLaunchKernelGGL(attn_tile_kernel<true>, dim3(ntiles, (H + 3) / 4), dim3(256), 0, stream,
                        reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const bf16_t*>(kc),
                        reinterpret_cast<const bf16_t*>(vc), row_slot, row_kvlen, tiles, reinterpret_cast<bf16_t*>(out),
                        ldo, H, t_max, n_slots, scale_log2);

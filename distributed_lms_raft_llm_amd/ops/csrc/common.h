@@ -46,6 +46,51 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
     return r;
 }
 
+// ------------------------------------------------------------------ fp8 (OCP e4m3fn) KV cache
+// The fp8 KV cache holds e4m3_rne(clamp(bf16 value, -448, 448)) bytes, no scales.  The clamp runs
+// in f32 ahead of the conversion, so the result does not depend on the instruction's overflow mode
+// and the NaN byte (0x7F / 0xFF) is never written (fmaxf / fminf also turn a NaN input into a bound).
+__device__ __forceinline__ float e4m3_clamp(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+
+// 8 bf16 (one staged 16-B chunk) -> 8 e4m3 bytes, element order kept
+__device__ __forceinline__ uint2 bf16x8_to_e4m3x8(const uint4 v) {
+    float f[8];
+    unpack8(v, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = e4m3_clamp(f[j]);
+    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    return make_uint2((unsigned int)lo, (unsigned int)hi);
+}
+
+// 4 e4m3 bytes -> 4 floats (exact), element order kept
+__device__ __forceinline__ void unpack4_e4m3(unsigned int w, float* f) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+}
+
+// 16 e4m3 bytes held in a uint4 -> 16 floats
+__device__ __forceinline__ void unpack16_e4m3(const uint4 v, float* f) {
+    unpack4_e4m3(v.x, f); unpack4_e4m3(v.y, f + 4); unpack4_e4m3(v.z, f + 8); unpack4_e4m3(v.w, f + 12);
+}
+
+// 8 e4m3 bytes -> 8 bf16 (exact: e4m3 has 3 mantissa bits and its subnormals are f32 normals, so the
+// upper half of the converted f32 is the value)
+__device__ __forceinline__ uint4 e4m3x8_to_bf16x8(const uint2 v) {
+    float f[8];
+    unpack4_e4m3(v.x, f);
+    unpack4_e4m3(v.y, f + 4);
+    uint4 r;
+    r.x = (__float_as_uint(f[0]) >> 16) | (__float_as_uint(f[1]) & 0xffff0000u);
+    r.y = (__float_as_uint(f[2]) >> 16) | (__float_as_uint(f[3]) & 0xffff0000u);
+    r.z = (__float_as_uint(f[4]) >> 16) | (__float_as_uint(f[5]) & 0xffff0000u);
+    r.w = (__float_as_uint(f[6]) >> 16) | (__float_as_uint(f[7]) & 0xffff0000u);
+    return r;
+}
+
 // Lane permute within 16-lane rows by DPP (a VALU operand modifier: no LDS round trip, unlike the
 // ds_bpermute_b32 that __shfl_xor compiles to -- six of those per reduction sat on the critical path
 // of every LayerNorm).  CTRL: 0xB1 quad_perm[1,0,3,2], 0x4E quad_perm[2,3,0,1], 0x141 row_half_mirror,
@@ -284,6 +329,7 @@ struct GemmEpi {
     const float* a_scale;
     const float* w_scale;
     int n_slots;  // EPI_QKV: KV-cache slots (the checked build range-checks row_slot against it)
+    int kv_fp8;   // EPI_QKV: k_cache / v_cache are e4m3 byte caches [slot][H][T][64] (64-B rows)
 };
 
 // Opt a kernel into > 64 KiB of dynamic LDS on the CURRENT device, once per (call site, device):

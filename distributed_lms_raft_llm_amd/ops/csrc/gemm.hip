@@ -111,7 +111,9 @@ __device__ __forceinline__ int qkv_chunk_row(int tid, int it, int r0, int M) {
     const int row = r0 + c / CPR;
     return row < M ? row : M - 1;
 }
-template <int CHUNKS, int NT, int CPR>
+// KV8: the caches are e4m3 byte caches (64-B key rows); a K/V chunk leaves the staging as 8 bytes
+// (bf16 -> clamp -> packed e4m3, common.h), q is unchanged.
+template <int CHUNKS, int NT, int CPR, bool KV8 = false>
 __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow, int tid, int r0, int c0, int M,
                                                      const GemmEpi& ep, const int (&sl)[(CHUNKS + NT - 1) / NT],
                                                      const int (&ps)[(CHUNKS + NT - 1) / NT]) {
@@ -127,6 +129,17 @@ __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow,
         const int col = c0 + ch * 8;
         const int part = col / ep.d_local;
         const int within = col - part * ep.d_local;
+        if constexpr (KV8) {
+            if (part != 0) {
+                const int head = within >> 6, dim = within & 63;
+                const size_t slot = dlms_idx(sl[it], ep.n_slots, CHK_QKV_SLOT);
+                const size_t pos = dlms_idx(ps[it], ep.t_max, CHK_QKV_POS);
+                unsigned char* d8 = reinterpret_cast<unsigned char*>(part == 1 ? ep.k_cache : ep.v_cache) +
+                                    ((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim;
+                *reinterpret_cast<uint2*>(d8) = bf16x8_to_e4m3x8(val);
+                continue;
+            }
+        }
         bf16_t* dst;
         if (part == 0) {
             dst = ep.q_out + (size_t)row * ep.ldq + within;
@@ -140,7 +153,7 @@ __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow,
     }
 }
 // ... with the indices loaded here, in one batch ahead of the stores (the 256x256 prefill kernel)
-template <int CHUNKS, int NT, int CPR>
+template <int CHUNKS, int NT, int CPR, bool KV8 = false>
 __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int tid, int r0, int c0, int M,
                                                  const GemmEpi& ep) {
     constexpr int ITER = (CHUNKS + NT - 1) / NT;
@@ -151,7 +164,7 @@ __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int
         sl[it] = ep.row_slot[row];
         ps[it] = ep.row_pos[row];
     }
-    qkv_staged_store_idx<CHUNKS, NT, CPR>(smem, srow, tid, r0, c0, M, ep, sl, ps);
+    qkv_staged_store_idx<CHUNKS, NT, CPR, KV8>(smem, srow, tid, r0, c0, M, ep, sl, ps);
 }
 
 // Launch geometry, computed once on the host (launch_gemm_cfg) so that the kernel's prologue holds no
@@ -189,7 +202,7 @@ __device__ __forceinline__ int xcd_remap_u(unsigned orig, unsigned nwg) {
     return (int)(xcd * q + (xcd < r ? xcd : r) + (orig >> 3));
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0>
+template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0, bool KV8 = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __restrict__ A,
                                                       const void* __restrict__ W, int lda, int ldw,
                                                       GemmGeo geo, int N, GemmEpi ep) {
@@ -198,6 +211,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
     constexpr int NW = WM * WN;  // waves per workgroup (4 or 8)
     constexpr int NT = 64 * NW;
     static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
+    static_assert(!KV8 || EPI == EPI_QKV, "KV8 is a mode of the QKV epilogue");
     constexpr int WTM = BM / WM;  // rows per wave
     constexpr int WTN = BN / WN;  // cols per wave
     constexpr int TM = WTM / 16;
@@ -595,9 +609,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
                 int sl[QITER], ps[QITER];
 #pragma unroll
                 for (int it = 0; it < QITER; ++it) sl[it] = (int)sl_pf[it], ps[it] = (int)ps_pf[it];
-                qkv_staged_store_idx<BM * CPR, NT, CPR>(smem, SROW, tid, m0, n0, M, ep, sl, ps);
+                qkv_staged_store_idx<BM * CPR, NT, CPR, KV8>(smem, SROW, tid, m0, n0, M, ep, sl, ps);
             } else {
-                qkv_staged_store<BM * CPR, NT, CPR>(smem, SROW, tid, m0, n0, M, ep);
+                qkv_staged_store<BM * CPR, NT, CPR, KV8>(smem, SROW, tid, m0, n0, M, ep);
             }
             return;
         }
@@ -651,7 +665,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
                         const size_t slot = dlms_idx(ep.row_slot[row], ep.n_slots, CHK_QKV_SLOT);
                         const size_t pos = dlms_idx(ep.row_pos[row], ep.t_max, CHK_QKV_POS);
                         const size_t idx = ((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim;
-                        (part == 1 ? ep.k_cache : ep.v_cache)[idx] = hv;
+                        if constexpr (KV8) {
+                            const float cv = e4m3_clamp(bf16_to_f32(hv));
+                            reinterpret_cast<unsigned char*>(part == 1 ? ep.k_cache : ep.v_cache)[idx] =
+                                (unsigned char)__builtin_amdgcn_cvt_pk_fp8_f32(cv, cv, 0, false);
+                        } else {
+                            (part == 1 ? ep.k_cache : ep.v_cache)[idx] = hv;
+                        }
                     }
                 }
             }
@@ -683,7 +703,7 @@ static std::atomic<long> g_tile_count[4][4];  // [BM 32/64/128/256][BN 64/96/128
 // everything the next buffer's four phases read.  K must be a multiple of 128 (an even number of
 // K-tiles).  It sums every output in the same k order as gemm_tn_kernel, so its results are
 // bit-identical to the 128x128 tiles' (tests/test_kernels_gpu.py).
-template <int EPI>
+template <int EPI, bool KV8 = false>
 __global__ __launch_bounds__(512) void gemm8p_kernel(const bf16_t* __restrict__ A, int lda,
                                                      const bf16_t* __restrict__ W, int ldw, int M, int N, int K,
                                                      GemmEpi ep) {
@@ -886,7 +906,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const bf16_t* __restrict__ 
             }
             __syncthreads();
             if constexpr (EPI == EPI_QKV) {
-                qkv_staged_store<128 * CPR, 512, CPR>(smem, SROW, tid, m0 + mq * 128, n0 + nq * 128, M, ep);
+                qkv_staged_store<128 * CPR, 512, CPR, KV8>(smem, SROW, tid, m0 + mq * 128, n0 + nq * 128, M, ep);
                 __syncthreads();
                 continue;
             }
@@ -912,7 +932,7 @@ static bool gemm8p_fits(int M, int lda, int N, int ldw) {
     return (size_t)M * lda * 2 < (1ull << 32) && (size_t)N * ldw * 2 < (1ull << 32);
 }
 
-template <int EPI>
+template <int EPI, bool KV8 = false>
 static hipError_t launch_gemm8p(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const GemmEpi& ep,
                                 hipStream_t stream) {
     const int split = EPI == EPI_PARTIAL ? ep.split_k : 1;
@@ -920,17 +940,17 @@ static hipError_t launch_gemm8p(const void* A, int lda, const void* W, int ldw, 
         return hipErrorInvalidValue;
     const size_t lds = 8 * 16384;  // >= the 128 x (128 x 4 + 16) B staged fp32 epilogue quadrant
     static std::atomic<uint64_t> attr_set{0};  // per device
-    if (hipError_t e = lds_opt_in(attr_set, reinterpret_cast<const void*>(&gemm8p_kernel<EPI>), (int)lds); e != hipSuccess)
+    if (hipError_t e = lds_opt_in(attr_set, reinterpret_cast<const void*>(&gemm8p_kernel<EPI, KV8>), (int)lds); e != hipSuccess)
         return e;
     g_tile_count[3][3].fetch_add(1, std::memory_order_relaxed);
     const int tiles = ((M + 255) / 256) * (N / 256) * split;
-    hipLaunchKernelGGL(gemm8p_kernel<EPI>, dim3(tiles), dim3(512), lds, stream, reinterpret_cast<const bf16_t*>(A), lda,
+    hipLaunchKernelGGL((gemm8p_kernel<EPI, KV8>), dim3(tiles), dim3(512), lds, stream, reinterpret_cast<const bf16_t*>(A), lda,
                        reinterpret_cast<const bf16_t*>(W), ldw, M, N, K, ep);
     return hipGetLastError();
 }
 
 
-template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0>
+template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0, bool KV8 = false>
 static hipError_t launch_gemm_cfg(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                                   const GemmEpi& ep, hipStream_t stream) {
     g_tile_count[BM <= 32 ? 0 : BM <= 64 ? 1 : BM <= 128 ? 2 : 3][BN <= 64 ? 0 : BN <= 96 ? 1 : BN <= 128 ? 2 : 3]
@@ -951,10 +971,10 @@ static hipError_t launch_gemm_cfg(const void* A, int lda, const void* W, int ldw
     const size_t stage_out = (size_t)BM * (BN * (EPI == EPI_PARTIAL ? 4 : 2) + 16);  // LDS-staged epilogue
     if (EPI != EPI_ARGMAX && EPI != EPI_F32 && stage_out > lds) lds = stage_out;
     static std::atomic<uint64_t> attr_set{0};  // > 64 KiB of dynamic LDS: opted into once per kernel and device
-    if (hipError_t e = lds_opt_in(attr_set, reinterpret_cast<const void*>(&gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE>),
+    if (hipError_t e = lds_opt_in(attr_set, reinterpret_cast<const void*>(&gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE, KV8>),
                                   (int)lds); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE>), dim3(tiles), dim3(64 * WM * WN), lds, stream, A,
+    hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE, KV8>), dim3(tiles), dim3(64 * WM * WN), lds, stream, A,
                        W, lda, ldw, geo, N, ep);
     return hipGetLastError();
 }
@@ -1043,11 +1063,12 @@ static hipError_t launch_forced(int id, const void* A, int lda, const void* W, i
     return hipSuccess;
 }
 
-template <int EPI, int IN>
+template <int EPI, int IN, bool KV8 = false>
 static hipError_t launch_gemm_epi(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                                   const GemmEpi& ep, hipStream_t stream) {
     const int split = EPI == EPI_PARTIAL ? ep.split_k : 1;
-    if (g_force_tile >= 0) {
+    // (the forced-tile tuning table is not instantiated for the fp8 KV cache: the heuristic's tiles are)
+    if (!KV8 && g_force_tile >= 0) {
         bool done = false;
         hipError_t e = launch_forced<EPI, IN>(g_force_tile, A, lda, W, ldw, M, N, K, ep, stream, &done);
         if (done) return e;
@@ -1072,14 +1093,14 @@ static hipError_t launch_gemm_epi(const void* A, int lda, const void* W, int ldw
         const int kc = K / split;
         if (M >= 16384 && N % 256 == 0 && kc % 128 == 0 && (EPI != EPI_PARTIAL || kc >= 1536) &&
             gemm8p_fits(M, lda, N, ldw))
-            return launch_gemm8p<EPI>(A, lda, W, ldw, M, N, K, ep, stream);
+            return launch_gemm8p<EPI, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     }
     if constexpr (IN == IN_BF16 && (EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF ||
                                     EPI == EPI_QKV || EPI == EPI_PARTIAL)) {
         // (only at the measured size class: 1024-prompt packed prefills; smaller admissions keep the
         // tiles below, e.g. a 4096-row out-projection would put 192 128x128 tiles on 256 CUs)
         if (M >= 16384 && N % 128 == 0)
-            return launch_gemm_cfg<128, 128, 2, 2, 2, EPI, IN, 3>(A, lda, W, ldw, M, N, K, ep, stream);
+            return launch_gemm_cfg<128, 128, 2, 2, 2, EPI, IN, 3, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     }
     // big prefill GEMMs with a bf16 epilogue: 256x256 tiles, 8 waves of 128x64 (one workgroup per
     // CU: its 128 KiB ring + 135 KiB staged epilogue), unless the last round of tiles would run
@@ -1088,7 +1109,7 @@ static hipError_t launch_gemm_epi(const void* A, int lda, const void* W, int ldw
     if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF || EPI == EPI_QKV) {
         const long t256 = (long)((M + 255) / 256) * (N / 256);
         if (N % 256 == 0 && M >= 4096 && (t256 <= 256 || t256 % 256 >= 128 || t256 >= 512)) {
-            return launch_gemm_cfg<256, 256, 2, 4, 2, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+            return launch_gemm_cfg<256, 256, 2, 4, 2, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
         }
     }
     // (LM head on a 512-row decode half: 256x256 tiles are 86.4 -> 78.3 us alone (N = 50432,
@@ -1101,7 +1122,7 @@ static hipError_t launch_gemm_epi(const void* A, int lda, const void* W, int ldw
     if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_GELU_ERF || EPI == EPI_QKV) {
         const long t128x64 = (long)((M + 127) / 128) * (N / 64);
         if (K >= 1024 && M >= 256 && t128x64 <= 256)
-            return launch_gemm_cfg<128, 64, 2, 2, 3, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+            return launch_gemm_cfg<128, 64, 2, 2, 3, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     }
     // decode row halves of the overlapped step (256 < M <= 512, K = 768 / 3072): 64x96 tiles in ONE
     // round of <= 256 workgroups -- QKV 192, c_fc 256, c_proj split 4 -> 256 -- so no CU streams two
@@ -1111,20 +1132,20 @@ static hipError_t launch_gemm_epi(const void* A, int lda, const void* W, int ldw
         (EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_QKV ||
          (EPI == EPI_PARTIAL && split == 4)) &&
         (long)((M + 63) / 64) * (N / 96) * split <= 256)
-        return launch_gemm_cfg<64, 96, 2, 2, 4, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+        return launch_gemm_cfg<64, 96, 2, 2, 4, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     if (EPI == EPI_PARTIAL && gemm96_on() && N == 768 && split == 4 && M > 256 && M <= 512 && K >= 2048)
-        return launch_gemm_cfg<64, 96, 2, 2, 4, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+        return launch_gemm_cfg<64, 96, 2, 2, 4, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     if (N % 128 == 0 && (t128 >= 1024 || (N >= 8192 && M >= 256)))
-        return launch_gemm_cfg<128, 128, 2, 2, 2, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+        return launch_gemm_cfg<128, 128, 2, 2, 2, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
     // few-row LM head (latency path, B <= 32): 32-row A tiles, so clamped copies of the few real rows
     // take a fifth of each ring stage instead of a third (batch 1: 34.86 -> 34.46 ms per query,
     // profiles/r2_lm_head_tiles_b1.txt)
     if (EPI == EPI_ARGMAX && M <= 32 && N % 128 == 0 && N >= 8192)
-        return launch_gemm_cfg<32, 128, 2, 2, 3, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
-    if (N % 128 == 0 && N >= 8192) return launch_gemm_cfg<64, 128, 2, 2, 3, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
-    if (M <= 64) return launch_gemm_cfg<32, 64, 2, 2, 6, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
-    if (t64 <= 400) return launch_gemm_cfg<64, 64, 2, 2, 4, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
-    return launch_gemm_cfg<64, 64, 2, 2, 2, EPI, IN>(A, lda, W, ldw, M, N, K, ep, stream);
+        return launch_gemm_cfg<32, 128, 2, 2, 3, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
+    if (N % 128 == 0 && N >= 8192) return launch_gemm_cfg<64, 128, 2, 2, 3, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
+    if (M <= 64) return launch_gemm_cfg<32, 64, 2, 2, 6, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
+    if (t64 <= 400) return launch_gemm_cfg<64, 64, 2, 2, 4, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
+    return launch_gemm_cfg<64, 64, 2, 2, 2, EPI, IN, 0, KV8>(A, lda, W, ldw, M, N, K, ep, stream);
 }
 
 extern "C" void dlms_gemm_force_tile(int id) { g_force_tile = id; }
@@ -1151,7 +1172,9 @@ extern "C" hipError_t dlms_gemm(int epi, const void* A, int lda, const void* W, 
         case EPI_GELU_TANH: return launch_gemm_epi<EPI_GELU_TANH, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
         case EPI_GELU_ERF: return launch_gemm_epi<EPI_GELU_ERF, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
         case EPI_F32: return launch_gemm_epi<EPI_F32, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
-        case EPI_QKV: return launch_gemm_epi<EPI_QKV, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
+        case EPI_QKV:
+            if (ep->kv_fp8) return launch_gemm_epi<EPI_QKV, IN_BF16, true>(A, lda, W, ldw, M, N, K, *ep, stream);
+            return launch_gemm_epi<EPI_QKV, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
         case EPI_ARGMAX: return launch_gemm_epi<EPI_ARGMAX, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
         case EPI_PARTIAL: return launch_gemm_epi<EPI_PARTIAL, IN_BF16>(A, lda, W, ldw, M, N, K, *ep, stream);
         default: return hipErrorInvalidValue;
@@ -1164,6 +1187,7 @@ extern "C" hipError_t dlms_gemm(int epi, const void* A, int lda, const void* W, 
 extern "C" hipError_t dlms_gemm_fp8(int epi, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                                     const GemmEpi* ep, hipStream_t stream) {
     if (K % (2 * GEMM_BK) != 0 || N % 64 != 0 || M <= 0 || !ep->a_scale || !ep->w_scale) return hipErrorInvalidValue;
+    if (epi == EPI_QKV && ep->kv_fp8) return hipErrorInvalidValue;  // no fp8-weights x fp8-cache build
     if (epi == EPI_PARTIAL && (ep->split_k < 1 || K % (ep->split_k * 2 * GEMM_BK) != 0)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_BF16: return launch_gemm_epi<EPI_BF16, IN_FP8>(A, lda, W, ldw, M, N, K, *ep, stream);

@@ -158,9 +158,14 @@ class TutoringServicer:
 
 
 def make_engine(model: str, device: str, max_batch: int, max_length: int, weights: str | None = None, seed: int = 0,
-                tp_group=None, weight_dtype: str = "bf16"):
+                tp_group=None, weight_dtype: str = "bf16", kv_dtype: str = "bf16"):
     """GPU: the HIP engine (TP over ``tp_group`` when given).  CPU: the torch reference engine, or
-    the sharded torch slot engine when a (gloo) TP group is given."""
+    the sharded torch slot engine when a (gloo) TP group is given.  ``kv_dtype="fp8"``: the e4m3 KV
+    cache (HIP engine) or its reference model (torch engine); not with a TP group."""
+    if kv_dtype == "fp8" and tp_group is not None:
+        from ..engine.gpt2_engine import kv_fp8_unsupported
+
+        raise ValueError(kv_fp8_unsupported(2, weight_dtype == "fp8"))
     cfg = gpt2_config(model)
     w = load_safetensors_weights(weights) if weights else init_gpt2_weights(cfg, seed=seed)
     if device == "auto":
@@ -169,14 +174,14 @@ def make_engine(model: str, device: str, max_batch: int, max_length: int, weight
         from ..engine.gpt2_engine import HipGPT2Engine
 
         return HipGPT2Engine(cfg, w, device=device, max_batch=max_batch, max_length=max_length, tp_group=tp_group,
-                             weight_dtype=weight_dtype)
+                             weight_dtype=weight_dtype, kv_dtype=kv_dtype)
     if tp_group is not None:
         from ..parallel.tp import TorchSlotEngine
 
         return TorchSlotEngine(cfg, w, group=tp_group, max_batch=max_batch or 8, max_length=max_length)
     from ..engine.gpt2_engine import TorchGPT2Engine
 
-    return TorchGPT2Engine(cfg, w, max_length=max_length)
+    return TorchGPT2Engine(cfg, w, max_length=max_length, kv_dtype=kv_dtype)
 
 
 def make_gate_worker(model: str, weights: str | None, device):
@@ -443,6 +448,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--repetition-penalty", type=float, default=1.2)
     ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: W8A8 e4m3 MFMA GEMMs for QKV / c_fc / LM head (GPU engine)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: the KV cache holds e4m3 bytes without scales -- half the bytes the decode attention "
+                         "streams, twice the slots in the same HBM, reduced precision; one GPU per replica, bf16 weights")
     ap.add_argument("--tp", type=int, default=0, help="tensor-parallel degree under torchrun (default: world)")
     ap.add_argument("--batching", choices=("auto", "continuous", "window"), default="auto")
     ap.add_argument("--chunk", type=int, default=8, help="decode steps between scheduler polls")
@@ -489,6 +497,12 @@ def main(argv=None):
         why = sampling_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
         if why:
             ap.error(f"--sample: {why}")
+    if args.kv_dtype == "fp8":
+        from ..engine.gpt2_engine import kv_fp8_unsupported
+
+        why = kv_fp8_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+        if why:
+            ap.error(f"--kv-dtype fp8: {why}")
     mode = {} if sampling is None else {"sampling": sampling}
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -527,7 +541,7 @@ def main(argv=None):
         src = dp_idx * tp
         device = f"cuda:{local}" if args.device != "cpu" and torch.cuda.is_available() else "cpu"
         eng = make_engine(args.model, device, args.max_batch, args.max_length, args.weights, tp_group=tp_group,
-                          weight_dtype=args.weight_dtype)
+                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
         if rank != src:
             n = serve_follower(eng, ctrl, src)
             log.info("TP follower rank %d done after %d commands", rank, n)
@@ -538,7 +552,7 @@ def main(argv=None):
         args.port += dp_idx
     else:
         eng = make_engine(args.model, args.device, args.max_batch, args.max_length, args.weights,
-                          weight_dtype=args.weight_dtype)
+                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
     args.max_batch = getattr(eng, "max_batch", 0) or args.max_batch or 64
     if args.warm_batch > 0 and hasattr(eng, "warm_decode_graphs"):
         # (a TP proxy mirrors the call to every rank of its group: the captures' warm-up steps run
