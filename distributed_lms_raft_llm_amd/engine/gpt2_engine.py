@@ -215,12 +215,15 @@ class HipGPT2Engine:
         """``kv_dtype="fp8"``: the KV cache holds OCP e4m3 bytes without scales
         (``models.gpt2.quantize_kv_e4m3``: the bf16 cache's content, saturated and rounded to
         nearest-even e4m3) -- half the bytes the decode attention streams and twice the slots per
-        GiB, at reduced precision (the oracle is ``GPT2Reference(kv_dtype="fp8")``).  Every batch
-        size then runs the tiled step (QKV GEMM scattering e4m3, the fp8 wave / persistent decode
-        attention, the fp8 tile attention in the prefill): the latency, mid, fused
-        attention-out-projection, fused-MLP and dataflow paths have no fp8-cache build and are off;
-        the overlapped >= 512-row step is on.  Not with ``tp_group`` or ``weight_dtype="fp8"``
-        (out of scope: ``ValueError``).  The bf16 default is the reference-precision cache.
+        GiB, at reduced precision (the oracle is ``GPT2Reference(kv_dtype="fp8")``).  By default
+        every batch size then runs the tiled step (QKV GEMM scattering e4m3, the fp8 wave /
+        persistent decode attention, the fp8 tile attention in the prefill) and the overlapped
+        >= 512-row step is on.  An explicit ``latency_path=True`` turns on the latency, mid, fused
+        attention-out-projection and fused-MLP paths on the fp8 cache under the rules of the bf16
+        cache (their QKV epilogues scatter e4m3, their attention kernels read it); the one-row
+        dataflow decode has no fp8-cache build and stays off.  Not with ``tp_group`` or
+        ``weight_dtype="fp8"`` (out of scope: ``ValueError``).  The bf16 default is the
+        reference-precision cache.
         ``weight_dtype="fp8"``: W8A8 OCP-e4m3 MFMA GEMMs for QKV, c_fc and the LM head (activation
         rows scaled by the fused LayerNorms); the bf16 default is the reference-precision path.
         ``overlap``: decode batches of >= ``overlap_min_batch`` rows run as ``overlap_parts`` row
@@ -332,11 +335,14 @@ class HipGPT2Engine:
         self._pseen: dict[tuple[int, int], int] = {}
         if self.overlap_parts not in (2, 3, 4):
             raise ValueError("overlap_parts: 2, 3 or 4 (one hardware queue each)")
+        # fp8 cache: the latency-shaped kernels (skinny / mid QKV scatter, split attention, fused
+        # attention + out-projection; the fused MLP never touches the cache) have e4m3-cache builds,
+        # but only an explicit ``latency_path=True`` turns them on -- the default engine keeps
+        # running the tiled step at every batch size
+        self.kv_fp8_latency = self.kv_fp8 and latency_path is True
         if latency_path is None:
             latency_path = os.environ.get("DLMS_LATENCY_PATH", "1") != "0"
-        if self.kv_fp8:
-            # the latency-shaped kernels (skinny / mid / fused attention + out-projection / fused MLP)
-            # scatter and read a bf16 cache: every batch size runs the tiled step
+        if self.kv_fp8 and not self.kv_fp8_latency:
             latency_path = False
         # (fp8 engines too: the latency path runs the bf16 weights the fp8 engine keeps beside its e4m3
         # copies -- at <= 8 rows the decode is bound by launch and dependency latency, not weight bytes;
@@ -375,9 +381,14 @@ class HipGPT2Engine:
         # residual in place -> [LN2 + c_fc + GELU] -> c_proj in place (ops/csrc/mid.hip: the
         # residual is complete whenever a LayerNorm needs it, so it runs in the GEMM's prologue and
         # no add+LN kernels or split-K slabs remain).  DLMS_MID_PATH=0: off.
+        # fp8 cache (latency_path=True): up to 32 rows by default.  The fp8 tiled step is faster than
+        # the bf16 one, and at the 48- and 64-row buckets it beats the mid path: 48.24 vs 48.67 ms and
+        # 49.40 vs 49.84 ms per 32 -> 150 generation (run-to-run spread 0.14 / 0.35 ms), against 47.77
+        # vs 43.22 ms at 32 rows -- profiles/r11_kv_fp8_latency.jsonl.  DLMS_MID_MAX_ROWS overrides.
         self.mid_max = 0
         if self.small_inplace and os.environ.get("DLMS_MID_PATH", "1") != "0":
-            self.mid_max = min(ops.mid_max_rows(cfg.n_embd), int(os.environ.get("DLMS_MID_MAX_ROWS", "64")))
+            self.mid_max = min(ops.mid_max_rows(cfg.n_embd),
+                               int(os.environ.get("DLMS_MID_MAX_ROWS", "32" if self.kv_fp8 else "64")))
         # attention fused with the out-projection for <= 4 rows (one launch fewer per layer); its
         # workgroups recompute a head's attention, so only for short caches
         # (TP=1: its per-head slabs are summed by the next fused add+LN kernel, 12 or 16 of them)
@@ -670,7 +681,7 @@ class HipGPT2Engine:
             return
         if r.tiles is not None:  # packed prompts (K6): 16-query MFMA tiles
             ops.tile_attention(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, r.tiles, out=r.att)
-        elif r.M * self.w.n_heads_local <= self.SPLIT_ATTN_MAX_PAIRS and not self.kv_fp8:
+        elif r.M * self.w.n_heads_local <= self.SPLIT_ATTN_MAX_PAIRS and (not self.kv_fp8 or self.kv_fp8_latency):
             # decode with few (row, head) pairs: split-K flash-decode puts NW waves on each pair's keys
             nw, ns = ops.attention_split_geometry(r.M * self.w.n_heads_local, self.max_length)
             ops.attention_split(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, out=r.att,

@@ -159,6 +159,9 @@ def _bind(L):
         "dlms_attention_split": [P, I, P, P, P, P, P, I, I, I, I, I, F, I, I, P, P, I, P],
         "dlms_attention_oproj": [P, I, P, P, P, P, I, I, I, I, F, P, I, I, P, I, ctypes.c_longlong, P],
         "dlms_attention_oproj_grouped": [P, P, P, P, P, I, I, I, I, F, P, I, I, P, ctypes.c_longlong, P],
+        "dlms_attention_split_fp8": [P, I, P, P, P, P, P, I, I, I, I, I, F, I, I, P, P, I, P],
+        "dlms_attention_oproj_fp8": [P, I, P, P, P, P, I, I, I, I, F, P, I, I, P, I, ctypes.c_longlong, P],
+        "dlms_attention_oproj_grouped_fp8": [P, P, P, P, P, I, I, I, I, F, P, I, I, P, ctypes.c_longlong, P],
         "dlms_skinny_addln_gemm": [I, P, P, I, P, I, ctypes.c_longlong, I, P, P, P, F, P, I, I, I,
                                    ctypes.POINTER(GemmEpi), I, ctypes.c_longlong, P, I, P],
         "dlms_skinny_mlp_cg": [I, I, I],
@@ -312,10 +315,23 @@ def _kv_dtype(k_cache: torch.Tensor, v_cache: torch.Tensor, what: str, fp8_ok: b
         raise ValueError(f"{what}: k_cache is {k_cache.dtype}, v_cache is {v_cache.dtype}: one cache dtype")
     if k_cache.dtype == FP8:
         if not fp8_ok:
-            raise ValueError(f"{what}: no fp8 KV-cache build of this path (the tiled QKV GEMM on bf16 weights, "
-                             f"the wave / persistent decode attention and the tile attention have one)")
+            raise ValueError(f"{what}: no fp8 KV-cache build of this path (the tiled, skinny and mid QKV GEMMs on "
+                             f"bf16 weights, the wave / persistent / split decode attention, the fused attention + "
+                             f"out-projection and the tile attention have one)")
         return True
     return False
+
+
+def _kv_caches(k_cache: torch.Tensor, v_cache: torch.Tensor, what: str) -> bool:
+    """``_kv_dtype`` plus the tensor checks of the latency-path kernels (skinny.hip / mid.hip): 4-D
+    GPU caches of the one dtype; an fp8 cache must be contiguous and 8-byte aligned (the kernels
+    address it as [slot][H][T][64] bytes and read 8-byte chunks)."""
+    kv8 = _kv_dtype(k_cache, v_cache, what)
+    for t, n in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+        _req(t, FP8 if kv8 else torch.bfloat16, n, 4)
+        if kv8 and (not t.is_contiguous() or t.data_ptr() % 8):
+            raise ValueError(f"{what}: the fp8 {n} must be contiguous and 8-byte aligned")
+    return kv8
 
 
 # ---------------------------------------------------------------------------------------------
@@ -879,8 +895,11 @@ def _skinny_epi(a: torch.Tensor, M: int, N: int, epi: int, bias, out, q_out, k_c
             raise ValueError("out too small")
         ep.out, ep.ldo = out.data_ptr(), out.stride(0)
     elif epi == EPI_QKV:
-        for t, n in ((q_out, "q_out"), (k_cache, "k_cache"), (v_cache, "v_cache")):
-            _req(t, torch.bfloat16, n)
+        kv8 = _kv_dtype(k_cache, v_cache, f"{name}(EPI_QKV)")
+        _req(q_out, torch.bfloat16, "q_out")
+        for t, n in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+            _req(t, FP8 if kv8 else torch.bfloat16, n)
+        ep.kv_fp8 = int(kv8)  # the launchers pick the kernels' e4m3 scatter (skinny_common.h SK_QKV8)
         _req(row_slot, torch.int32, "row_slot", 1)
         _req(row_pos, torch.int32, "row_pos", 1)
         if N % 3 or (N // 3) % 64:
@@ -921,7 +940,9 @@ def skinny_gemm(a: torch.Tensor, w_sh: torch.Tensor, epi: int, *, ln=None, bias=
     EPI_F32 adds ``acc + bias`` into ``out`` (f32 [M, N], in place: the residual stream; an int64
     ``out`` is copy 0 of ``skinny_mlp``'s fixed-point residual and gets fix(acc + bias) added);
     EPI_PARTIAL stores the raw f32 partial (TP); EPI_ARGMAX writes one key per (row, 64 columns)
-    into ``argmax_out`` [M, >= N/64] exactly like ``gemm(..., EPI_ARGMAX)``."""
+    into ``argmax_out`` [M, >= N/64] exactly like ``gemm(..., EPI_ARGMAX)``.  EPI_QKV scatters K / V
+    into bf16 caches or, by the cache tensors' dtype, into the fp8 (e4m3) byte caches
+    (``models.gpt2.quantize_kv_e4m3`` of the bf16 value; also ``skinny_addln_gemm`` / ``mid_ln_gemm``)."""
     _req(w_sh, torch.bfloat16, "w_sh", 4)
     G, KB = w_sh.shape[0], w_sh.shape[1]
     if w_sh.shape[2] != 64 or w_sh.shape[3] != 8 or not w_sh.is_contiguous():
@@ -1112,8 +1133,11 @@ def skinny_addln_gemm(x_in: torch.Tensor, w_sh: torch.Tensor, epi: int, gamma, b
             raise ValueError("out too small")
         ep.out, ep.ldo = out.data_ptr(), out.stride(0)
     elif epi == EPI_QKV:
-        for t, n in ((q_out, "q_out"), (k_cache, "k_cache"), (v_cache, "v_cache")):
-            _req(t, torch.bfloat16, n)
+        kv8 = _kv_dtype(k_cache, v_cache, "skinny_addln_gemm(EPI_QKV)")
+        _req(q_out, torch.bfloat16, "q_out")
+        for t, n in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+            _req(t, FP8 if kv8 else torch.bfloat16, n)
+        ep.kv_fp8 = int(kv8)  # the launchers pick the kernels' e4m3 scatter (skinny_common.h SK_QKV8)
         _req(row_slot, torch.int32, "row_slot", 1)
         _req(row_pos, torch.int32, "row_pos", 1)
         if N % 3 or (N // 3) % 64:
@@ -1306,10 +1330,11 @@ def attention_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
                     sync: int | None = None):
     """Split-K flash-decode: ``splits`` workgroups of ``waves`` waves per (row, head), each wave
     streaming a slice of the keys; waves merge by log-sum-exp in LDS, workgroups through a
-    workspace merged by the last to arrive.  Same contract as ``row_attention``."""
+    workspace merged by the last to arrive.  Same contract as ``row_attention``; the caches are
+    bf16 or the fp8 (e4m3) byte cache (same lane mapping with 8-byte loads and exact widening: the
+    result is bit for bit the bf16 kernel's on ``cache.to(torch.bfloat16)``)."""
     _req(q, torch.bfloat16, "q", 2)
-    _req(k_cache, torch.bfloat16, "k_cache", 4)
-    _req(v_cache, torch.bfloat16, "v_cache", 4)
+    kv8 = _kv_caches(k_cache, v_cache, "attention_split")
     _req(row_slot, torch.int32, "row_slot", 1)
     _req(row_kvlen, torch.int32, "row_kvlen", 1)
     R = q.shape[0]
@@ -1333,10 +1358,10 @@ def attention_split(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
             raise ValueError("attention_split: workspace too small")
         ws_p, cnt_p = _p(workspace.partials), _p(workspace.counters)
     sc = (1.0 / 8.0) if scale is None else scale
-    _check(lib().dlms_attention_split(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen),
-                                      _p(out), out.stride(0), R, H, T, S, float(sc), int(waves), int(splits),
-                                      ws_p, cnt_p, ATTN_SPLIT_SYNC if sync is None else int(sync), _stream()),
-           "attention_split")
+    fn = lib().dlms_attention_split_fp8 if kv8 else lib().dlms_attention_split
+    _check(fn(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), _p(out), out.stride(0), R, H, T,
+              S, float(sc), int(waves), int(splits), ws_p, cnt_p, ATTN_SPLIT_SYNC if sync is None else int(sync),
+              _stream()), "attention_split")
     return out
 
 
@@ -1356,10 +1381,9 @@ def attention_oproj(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     """Decode attention fused with the out-projection (M <= 4 rows): head h's share
     ``attn_h(q) @ W_o[:, 64h:64h+64]^T`` goes to ``parts[h, :M, :N]`` (fp32 split-K slabs; no bias),
     so ``parts[:H].sum(0)`` is the out-projection -- what the next fused add+LN kernel sums with
-    ``nsplit=H``.  ``wo_sh`` is ``shuffle_weight(W_o)`` with W_o [N, H*64]."""
+    ``nsplit=H``.  ``wo_sh`` is ``shuffle_weight(W_o)`` with W_o [N, H*64].  Caches: bf16 or fp8."""
     _req(q, torch.bfloat16, "q", 2)
-    _req(k_cache, torch.bfloat16, "k_cache", 4)
-    _req(v_cache, torch.bfloat16, "v_cache", 4)
+    kv8 = _kv_caches(k_cache, v_cache, "attention_oproj")
     _req(row_slot, torch.int32, "row_slot", 1)
     _req(row_kvlen, torch.int32, "row_kvlen", 1)
     _req(wo_sh, torch.bfloat16, "wo_sh", 4)
@@ -1377,9 +1401,9 @@ def attention_oproj(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         raise ValueError("attention_oproj: index arrays too short")
     nt = attention_oproj_tiles(N) if tiles is None else tiles
     sc = (1.0 / 8.0) if scale is None else scale
-    _check(lib().dlms_attention_oproj(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), M,
-                                      H, T, S, float(sc), _p(wo_sh), N, int(nt), _p(parts), parts.stride(1),
-                                      parts.stride(0), _stream()),
+    fn = lib().dlms_attention_oproj_fp8 if kv8 else lib().dlms_attention_oproj
+    _check(fn(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), M, H, T, S, float(sc),
+              _p(wo_sh), N, int(nt), _p(parts), parts.stride(1), parts.stride(0), _stream()),
            "attention_oproj")
     return parts
 
@@ -1388,10 +1412,10 @@ def attention_oproj_grouped(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
                             row_kvlen: torch.Tensor, wo_sh: torch.Tensor, parts: torch.Tensor, heads_per_group: int,
                             scale: float | None = None, tiles: int = 3) -> torch.Tensor:
     """``attention_oproj`` for ONE row with heads in groups of ``heads_per_group`` (3 or 4): group g's
-    share of the out-projection goes to ``parts[g, 0, :N]`` -- H / heads_per_group slabs."""
+    share of the out-projection goes to ``parts[g, 0, :N]`` -- H / heads_per_group slabs.  Caches:
+    bf16 or fp8."""
     _req(q, torch.bfloat16, "q", 2)
-    _req(k_cache, torch.bfloat16, "k_cache", 4)
-    _req(v_cache, torch.bfloat16, "v_cache", 4)
+    kv8 = _kv_caches(k_cache, v_cache, "attention_oproj_grouped")
     _req(row_slot, torch.int32, "row_slot", 1)
     _req(row_kvlen, torch.int32, "row_kvlen", 1)
     _req(wo_sh, torch.bfloat16, "wo_sh", 4)
@@ -1408,9 +1432,9 @@ def attention_oproj_grouped(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     if parts.shape[0] < H // hg or parts.shape[2] < N or parts.stride(2) != 1:
         raise ValueError("attention_oproj_grouped: parts must be [>= H/hg, >= 1, >= N]")
     sc = (1.0 / 8.0) if scale is None else scale
-    _check(lib().dlms_attention_oproj_grouped(_p(q), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), H, hg, T,
-                                              S, float(sc), _p(wo_sh), N, int(tiles), _p(parts), parts.stride(0),
-                                              _stream()),
+    fn = lib().dlms_attention_oproj_grouped_fp8 if kv8 else lib().dlms_attention_oproj_grouped
+    _check(fn(_p(q), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen), H, hg, T, S, float(sc), _p(wo_sh), N,
+              int(tiles), _p(parts), parts.stride(0), _stream()),
            "attention_oproj_grouped")
     return parts
 

@@ -407,7 +407,9 @@ extern "C" hipError_t dlms_mid_ln_gemm(int epi, const float* x, int ldx, const f
     if (M <= 0 || M > dlms_mid_max_rows(K) || N % 16 || ldx % 4 || ldx < K) return hipErrorInvalidValue;
     const bf16_t* W = reinterpret_cast<const bf16_t*>(Wsh);
     switch (epi) {
-        case SK_QKV: return mid::by_shape<SK_QKV>(geo, x, ldx, gamma, beta, eps, W, M, N, K, *ep, stream);
+        case SK_QKV:  // GemmEpi::kv_fp8: the e4m3 byte caches (SK_QKV8)
+            if (ep->kv_fp8) return mid::by_shape<SK_QKV8>(geo, x, ldx, gamma, beta, eps, W, M, N, K, *ep, stream);
+            return mid::by_shape<SK_QKV>(geo, x, ldx, gamma, beta, eps, W, M, N, K, *ep, stream);
         case SK_GELU_TANH: return mid::by_shape<SK_GELU_TANH>(geo, x, ldx, gamma, beta, eps, W, M, N, K, *ep, stream);
         case SK_BF16: return mid::by_shape<SK_BF16>(geo, x, ldx, gamma, beta, eps, W, M, N, K, *ep, stream);
         default: return hipErrorInvalidValue;

@@ -287,7 +287,10 @@ extern "C" hipError_t dlms_skinny_gemm(int epi, const void* A, int lda, const fl
             return ln ? skinny_mt<SK_BF16, true>(A, lda, ln_g, ln_b, eps, W, M, N, K, *ep, stream)
                       : skinny_mt<SK_BF16, false>(A, lda, ln_g, ln_b, eps, W, M, N, K, *ep, stream);
         SK_LN(SK_GELU_TANH)
-        SK_LN(SK_QKV)
+        case SK_QKV:  // GemmEpi::kv_fp8: the e4m3 byte caches (SK_QKV8)
+            if (!ln) return hipErrorInvalidValue;
+            return ep->kv_fp8 ? skinny_mt<SK_QKV8, true>(A, lda, ln_g, ln_b, eps, W, M, N, K, *ep, stream)
+                              : skinny_mt<SK_QKV, true>(A, lda, ln_g, ln_b, eps, W, M, N, K, *ep, stream);
         SK_NOLN(SK_F32)
         SK_NOLN(SK_FIXADD)
         case SK_ARGMAX:  // with the LN prologue: ln_f fused into the latency path's LM head
@@ -624,14 +627,21 @@ extern "C" hipError_t dlms_skinny_addln_gemm(int epi, const void* x_in, float* x
     const AddlnArgs a{x_in, x_out, ldx, parts, ldp, split_stride, res_bias, gamma, beta, eps,
                       reinterpret_cast<const bf16_t*>(Wsh), M, N, K, reinterpret_cast<uint4*>(zero_buf),
                       zero_buf ? zero_chunks : 0, xcs};
+    const bool kv8 = epi == SK_QKV && ep->kv_fp8;  // the e4m3 byte caches: the SK_QKV8 instantiations
     if (xfix) {
-        switch ((K / 4 + 63) / 64) {
-            case 3: return addln_rpw<SK_QKV, 0, 3, true>(a, *ep, stream);
-            case 4: return addln_rpw<SK_QKV, 0, 4, true>(a, *ep, stream);
-            case 5: return addln_rpw<SK_QKV, 0, 5, true>(a, *ep, stream);
-            case 7: return addln_rpw<SK_QKV, 0, 7, true>(a, *ep, stream);
-            default: return hipErrorInvalidValue;
+#define ADDLN_XFIX(E)                                                       \
+    switch ((K / 4 + 63) / 64) {                                            \
+        case 3: return addln_rpw<E, 0, 3, true>(a, *ep, stream);            \
+        case 4: return addln_rpw<E, 0, 4, true>(a, *ep, stream);            \
+        case 5: return addln_rpw<E, 0, 5, true>(a, *ep, stream);            \
+        case 7: return addln_rpw<E, 0, 7, true>(a, *ep, stream);            \
+        default: return hipErrorInvalidValue;                               \
+    }
+        if (kv8) {
+            ADDLN_XFIX(SK_QKV8)
         }
+        ADDLN_XFIX(SK_QKV)
+#undef ADDLN_XFIX
     }
 #define ADDLN(E, NS) return addln_nv4<E, NS>(a, *ep, stream)
 #define ADDLN_EPI(E)                    \
@@ -644,7 +654,11 @@ extern "C" hipError_t dlms_skinny_addln_gemm(int epi, const void* x_in, float* x
         default: return hipErrorInvalidValue; \
     }
     switch (epi) {
-        case SK_QKV: ADDLN_EPI(SK_QKV)
+        case SK_QKV:
+            if (kv8) {
+                ADDLN_EPI(SK_QKV8)
+            }
+            ADDLN_EPI(SK_QKV)
         case SK_GELU_TANH: ADDLN_EPI(SK_GELU_TANH)
         default: return hipErrorInvalidValue;
     }
@@ -985,9 +999,59 @@ extern "C" hipError_t dlms_ln_fix(const void* x, int ldx, long long xcs, const f
 // lane&7) owns dims [8c, 8c+8) of keys 8i + g), then a log-sum-exp merge of the NW partial
 // (max, sum, acc[64]) triples in a fixed order through LDS.  At batch 1 and 1024 cached keys this
 // puts 12 x NW waves on the KV stream instead of 12.
+// One lane's 8-dim chunk of a key / value row: 16 bytes of the bf16 cache, or (KV8) 8 bytes of the fp8
+// (OCP e4m3, no scales) byte cache [slot][H][T][64] with 64-byte key rows.  The lane mapping, q, the
+// online softmax and the merges are the same for both; only the load width and the (exact) widening
+// differ, so a kernel's fp8 build computes bit for bit what its bf16 build computes on the widened cache.
+template <bool KV8>
+struct KvChunk {
+    typedef uint4 type;
+};
+template <>
+struct KvChunk<true> {
+    typedef uint2 type;
+};
+
+// the cache's element: bf16, or one e4m3 byte
+template <bool KV8>
+using kv_elem_t = std::conditional_t<KV8, unsigned char, bf16_t>;
+
+template <bool KV8>
+__device__ __forceinline__ const kv_elem_t<KV8>* kv_cache_ptr(const bf16_t* cache) {
+    return reinterpret_cast<const kv_elem_t<KV8>*>(cache);
+}
+
+// the chunk at p (dims [8c, 8c + 8) of one key); NT: non-temporal (a once-read stream)
+template <bool KV8, bool NT>
+__device__ __forceinline__ typename KvChunk<KV8>::type kv_chunk_load(const kv_elem_t<KV8>* p) {
+    if constexpr (KV8) {
+        if constexpr (NT) {
+            typedef unsigned int u32x2n_t __attribute__((ext_vector_type(2)));
+            const u32x2n_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x2n_t*>(p));
+            return make_uint2(a.x, a.y);
+        } else {
+            return *reinterpret_cast<const uint2*>(p);
+        }
+    } else {
+        if constexpr (NT) {
+            typedef unsigned int u32x4n_t __attribute__((ext_vector_type(4)));
+            const u32x4n_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4n_t*>(p));
+            return make_uint4(a.x, a.y, a.z, a.w);
+        } else {
+            return *reinterpret_cast<const uint4*>(p);
+        }
+    }
+}
+
+__device__ __forceinline__ void kv_unpack8(const uint4 v, float* f) { unpack8(v, f); }
+__device__ __forceinline__ void kv_unpack8(const uint2 v, float* f) {
+    unpack4_e4m3(v.x, f);
+    unpack4_e4m3(v.y, f + 4);
+}
+
 constexpr int ATTN_WS_STRIDE = 68;  // floats per partial: m, l, pad, pad, o[64] (16-byte aligned o)
 
-template <int NW, int SYNC>
+template <int NW, int SYNC, bool KV8 = false>
 __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const bf16_t* __restrict__ q, int ldq,
                                                            const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
                                                            const int* __restrict__ row_slot,
@@ -1013,8 +1077,8 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const bf16_t* __res
     const int t_lo = w_lo + wave * span < w_hi ? w_lo + wave * span : w_hi;
     const int t_hi = t_lo + span < w_hi ? t_lo + span : w_hi;
     const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
-    const bf16_t* K = kc + head_off + c * 8;
-    const bf16_t* V = vc + head_off + c * 8;
+    const kv_elem_t<KV8>* K = kv_cache_ptr<KV8>(kc) + head_off + c * 8;
+    const kv_elem_t<KV8>* V = kv_cache_ptr<KV8>(vc) + head_off + c * 8;
 
     float qf[8];
     unpack8(*reinterpret_cast<const uint4*>(q + (size_t)r * ldq + h * 64 + c * 8), qf);
@@ -1026,21 +1090,18 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const bf16_t* __res
 
     constexpr int U = 4;  // key groups of 8 in flight per wave (profiles/r2_attn_split_unroll.txt)
     for (int t0 = t_lo; t0 < t_hi; t0 += 8 * U) {
-        uint4 kr[U], vr[U];
+        typename KvChunk<KV8>::type kr[U], vr[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             int t = t0 + u * 8 + g;
-            t = t < t_hi ? t : t_hi - 1;
-            typedef unsigned int u32x4n_t __attribute__((ext_vector_type(4)));
-            const u32x4n_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4n_t*>(K + (size_t)t * 64));
-            const u32x4n_t b = __builtin_nontemporal_load(reinterpret_cast<const u32x4n_t*>(V + (size_t)t * 64));
-            kr[u] = make_uint4(a.x, a.y, a.z, a.w);
-            vr[u] = make_uint4(b.x, b.y, b.z, b.w);
+            t = t < t_hi ? t : t_hi - 1;  // (never a key past kvlen: the fp8 cache may hold the NaN byte there)
+            kr[u] = kv_chunk_load<KV8, true>(K + (size_t)t * 64);
+            vr[u] = kv_chunk_load<KV8, true>(V + (size_t)t * 64);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float kf[8];
-            unpack8(kr[u], kf);
+            kv_unpack8(kr[u], kf);
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) s += qf[j] * kf[j];
@@ -1050,7 +1111,7 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const bf16_t* __res
                 const float corr = exp2f(m - m_new);
                 const float p = exp2f(s - m_new);
                 float vf[8];
-                unpack8(vr[u], vf);
+                kv_unpack8(vr[u], vf);
                 l = l * corr + p;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] = acc[j] * corr + p * vf[j];
@@ -1155,10 +1216,11 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const bf16_t* __res
     if (lane == 0) atomicExch(cnt + r * H + h, 0);
 }
 
-extern "C" hipError_t dlms_attention_split(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
-                                           const int* row_kvlen, void* out, int ldo, int R, int H, int t_max,
-                                           int n_slots, float scale, int nw, int ns, float* ws, int* cnt,
-                                           int sync, hipStream_t stream) {
+template <bool KV8>
+static hipError_t attention_split_launch(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
+                                         const int* row_kvlen, void* out, int ldo, int R, int H, int t_max,
+                                         int n_slots, float scale, int nw, int ns, float* ws, int* cnt, int sync,
+                                         hipStream_t stream) {
     if (R <= 0 || H <= 0 || t_max <= 0 || ns < 1 || ns > 64) return hipErrorInvalidValue;
     if (ns > 1 && (ws == nullptr || cnt == nullptr)) return hipErrorInvalidValue;
     const float sl2 = scale * 1.4426950408889634f;
@@ -1170,10 +1232,10 @@ extern "C" hipError_t dlms_attention_split(const void* q, int ldq, const void* k
     auto pick = [&](auto sync_c) -> bool {
         constexpr int S = decltype(sync_c)::value;
         switch (nw) {
-            case 2: go(attn_split_kernel<2, S>, 128); return true;
-            case 4: go(attn_split_kernel<4, S>, 256); return true;
-            case 8: go(attn_split_kernel<8, S>, 512); return true;
-            case 16: go(attn_split_kernel<16, S>, 1024); return true;
+            case 2: go(attn_split_kernel<2, S, KV8>, 128); return true;
+            case 4: go(attn_split_kernel<4, S, KV8>, 256); return true;
+            case 8: go(attn_split_kernel<8, S, KV8>, 512); return true;
+            case 16: go(attn_split_kernel<16, S, KV8>, 1024); return true;
             default: return false;
         }
     };
@@ -1182,6 +1244,23 @@ extern "C" hipError_t dlms_attention_split(const void* q, int ldq, const void* k
                         : pick(std::integral_constant<int, 2>{});
     if (!ok) return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_attention_split(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
+                                           const int* row_kvlen, void* out, int ldo, int R, int H, int t_max,
+                                           int n_slots, float scale, int nw, int ns, float* ws, int* cnt,
+                                           int sync, hipStream_t stream) {
+    return attention_split_launch<false>(q, ldq, kc, vc, row_slot, row_kvlen, out, ldo, R, H, t_max, n_slots, scale, nw,
+                                         ns, ws, cnt, sync, stream);
+}
+
+// kc / vc: the fp8 (e4m3) byte caches [slots][H][t_max][64], 8-byte aligned
+extern "C" hipError_t dlms_attention_split_fp8(const void* q, int ldq, const void* kc, const void* vc,
+                                               const int* row_slot, const int* row_kvlen, void* out, int ldo, int R,
+                                               int H, int t_max, int n_slots, float scale, int nw, int ns, float* ws,
+                                               int* cnt, int sync, hipStream_t stream) {
+    return attention_split_launch<true>(q, ldq, kc, vc, row_slot, row_kvlen, out, ldo, R, H, t_max, n_slots, scale, nw,
+                                        ns, ws, cnt, sync, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1197,7 +1276,7 @@ extern "C" hipError_t dlms_attention_split(const void* q, int ldq, const void* k
 // slabs in fixed order (deterministic).  (Summing them here instead -- write-through partials +
 // an arrival counter + last-arriver reduce -- measured 11.8 us per call against 5.5 + 5.1 for the
 // two kernels it replaced: three dependent global round trips cost what a launch boundary does.)
-template <int NT>
+template <int NT, bool KV8 = false>
 __global__ __launch_bounds__(256) void attn_oproj_kernel(
     const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int* __restrict__ row_slot, const int* __restrict__ row_kvlen, int M, int H, int t_max, int n_slots,
@@ -1240,25 +1319,25 @@ __global__ __launch_bounds__(256) void attn_oproj_kernel(
         const int t_lo = sl * span < kvlen ? sl * span : kvlen;
         const int t_hi = t_lo + span < kvlen ? t_lo + span : kvlen;
         const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
-        const bf16_t* K = kc + head_off + c * 8;
-        const bf16_t* V = vc + head_off + c * 8;
+        const kv_elem_t<KV8>* K = kv_cache_ptr<KV8>(kc) + head_off + c * 8;
+        const kv_elem_t<KV8>* V = kv_cache_ptr<KV8>(vc) + head_off + c * 8;
         float qf[8];
         unpack8(*reinterpret_cast<const uint4*>(q + (size_t)row * ldq + h * 64 + c * 8), qf);
 #pragma unroll
         for (int e = 0; e < 8; ++e) qf[e] *= scale_log2;
         for (int t0 = t_lo; t0 < t_hi; t0 += 8 * U) {
-            uint4 kr[U], vr[U];
+            typename KvChunk<KV8>::type kr[U], vr[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 int t = t0 + u * 8 + g;
                 t = t < t_hi ? t : t_hi - 1;
-                kr[u] = *reinterpret_cast<const uint4*>(K + (size_t)t * 64);
-                vr[u] = *reinterpret_cast<const uint4*>(V + (size_t)t * 64);
+                kr[u] = kv_chunk_load<KV8, false>(K + (size_t)t * 64);
+                vr[u] = kv_chunk_load<KV8, false>(V + (size_t)t * 64);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 float kf[8];
-                unpack8(kr[u], kf);
+                kv_unpack8(kr[u], kf);
                 float sc = 0.f;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) sc += qf[e] * kf[e];
@@ -1268,7 +1347,7 @@ __global__ __launch_bounds__(256) void attn_oproj_kernel(
                     const float corr = exp2f(m - m_new);
                     const float p = exp2f(sc - m_new);
                     float vf[8];
-                    unpack8(vr[u], vf);
+                    kv_unpack8(vr[u], vf);
                     l = l * corr + p;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] = acc[e] * corr + p * vf[e];
@@ -1351,7 +1430,7 @@ __global__ __launch_bounds__(256) void attn_oproj_kernel(
 // split-K slabs the fused add+LN kernel already sums (12 slabs cost that kernel ~2 us at batch 1).
 // (Groups of 5 heads at 2 waves per head for GPT-2-large / XL measured slower than the split
 // attention + in-place out-projection: profiles/r5_large_xl_hg5_tiles_ab.jsonl.)
-template <int HG, int NT, int WPH>
+template <int HG, int NT, int WPH, bool KV8 = false>
 __global__ __launch_bounds__(64 * WPH * HG) void attn_oproj_hg_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int* __restrict__ row_slot, const int* __restrict__ row_kvlen, int H, int t_max, int n_slots,
@@ -1389,8 +1468,8 @@ __global__ __launch_bounds__(64 * WPH * HG) void attn_oproj_hg_kernel(
     const int t_lo = sl * span < kvlen ? sl * span : kvlen;
     const int t_hi = t_lo + span < kvlen ? t_lo + span : kvlen;
     const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
-    const bf16_t* K = kc + head_off + c * 8;
-    const bf16_t* V = vc + head_off + c * 8;
+    const kv_elem_t<KV8>* K = kv_cache_ptr<KV8>(kc) + head_off + c * 8;
+    const kv_elem_t<KV8>* V = kv_cache_ptr<KV8>(vc) + head_off + c * 8;
     float qf[8];
     unpack8(*reinterpret_cast<const uint4*>(q + h * 64 + c * 8), qf);
 #pragma unroll
@@ -1398,18 +1477,18 @@ __global__ __launch_bounds__(64 * WPH * HG) void attn_oproj_hg_kernel(
     float m = -INFINITY, l = 0.f;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int t0 = t_lo; t0 < t_hi; t0 += 8 * U) {
-        uint4 kr[U], vr[U];
+        typename KvChunk<KV8>::type kr[U], vr[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             int t = t0 + u * 8 + g;
             t = t < t_hi ? t : t_hi - 1;
-            kr[u] = *reinterpret_cast<const uint4*>(K + (size_t)t * 64);
-            vr[u] = *reinterpret_cast<const uint4*>(V + (size_t)t * 64);
+            kr[u] = kv_chunk_load<KV8, false>(K + (size_t)t * 64);
+            vr[u] = kv_chunk_load<KV8, false>(V + (size_t)t * 64);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float kf[8];
-            unpack8(kr[u], kf);
+            kv_unpack8(kr[u], kf);
             float sc = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) sc += qf[e] * kf[e];
@@ -1419,7 +1498,7 @@ __global__ __launch_bounds__(64 * WPH * HG) void attn_oproj_hg_kernel(
                 const float corr = exp2f(m - m_new);
                 const float p = exp2f(sc - m_new);
                 float vf[8];
-                unpack8(vr[u], vf);
+                kv_unpack8(vr[u], vf);
                 l = l * corr + p;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] = acc[e] * corr + p * vf[e];
@@ -1488,10 +1567,11 @@ __global__ __launch_bounds__(64 * WPH * HG) void attn_oproj_hg_kernel(
     if (gg == 0) part[(size_t)grp * split_stride + (j * NT + wave) * 16 + fr] = d[0];  // row 0 of the tile
 }
 
-extern "C" hipError_t dlms_attention_oproj_grouped(const void* q, const void* kc, const void* vc, const int* row_slot,
-                                                   const int* row_kvlen, int H, int hg, int t_max, int n_slots,
-                                                   float scale, const void* wo_sh, int N, int nt, float* part,
-                                                   long long split_stride, hipStream_t stream) {
+template <bool KV8>
+static hipError_t attention_oproj_grouped_launch(const void* q, const void* kc, const void* vc, const int* row_slot,
+                                                 const int* row_kvlen, int H, int hg, int t_max, int n_slots,
+                                                 float scale, const void* wo_sh, int N, int nt, float* part,
+                                                 long long split_stride, hipStream_t stream) {
     if (H < 1 || hg < 1 || H % hg || t_max < 1 || N % 16 || nt < 1 || nt > 4 * hg || (N / 16) % nt)
         return hipErrorInvalidValue;
     const float sl2 = scale * 1.4426950408889634f;
@@ -1503,16 +1583,34 @@ extern "C" hipError_t dlms_attention_oproj_grouped(const void* q, const void* kc
                            split_stride);
     };
 #define AOG(HG_, NT_, WPH_) \
-    if (hg == HG_ && nt == NT_) { go(attn_oproj_hg_kernel<HG_, NT_, WPH_>, 64 * WPH_ * HG_); return hipGetLastError(); }
+    if (hg == HG_ && nt == NT_) { go(attn_oproj_hg_kernel<HG_, NT_, WPH_, KV8>, 64 * WPH_ * HG_); return hipGetLastError(); }
     AOG(3, 1, 4) AOG(3, 2, 4) AOG(3, 3, 4) AOG(3, 4, 4) AOG(4, 1, 4) AOG(4, 2, 4) AOG(4, 3, 4) AOG(4, 4, 4)
 #undef AOG
     return hipErrorInvalidValue;
 }
 
-extern "C" hipError_t dlms_attention_oproj(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
-                                           const int* row_kvlen, int M, int H, int t_max, int n_slots, float scale,
-                                           const void* wo_sh, int N, int nt, float* part, int ldp,
-                                           long long split_stride, hipStream_t stream) {
+extern "C" hipError_t dlms_attention_oproj_grouped(const void* q, const void* kc, const void* vc, const int* row_slot,
+                                                   const int* row_kvlen, int H, int hg, int t_max, int n_slots,
+                                                   float scale, const void* wo_sh, int N, int nt, float* part,
+                                                   long long split_stride, hipStream_t stream) {
+    return attention_oproj_grouped_launch<false>(q, kc, vc, row_slot, row_kvlen, H, hg, t_max, n_slots, scale, wo_sh, N,
+                                                 nt, part, split_stride, stream);
+}
+
+extern "C" hipError_t dlms_attention_oproj_grouped_fp8(const void* q, const void* kc, const void* vc,
+                                                       const int* row_slot, const int* row_kvlen, int H, int hg,
+                                                       int t_max, int n_slots, float scale, const void* wo_sh, int N,
+                                                       int nt, float* part, long long split_stride,
+                                                       hipStream_t stream) {
+    return attention_oproj_grouped_launch<true>(q, kc, vc, row_slot, row_kvlen, H, hg, t_max, n_slots, scale, wo_sh, N,
+                                                nt, part, split_stride, stream);
+}
+
+template <bool KV8>
+static hipError_t attention_oproj_launch(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
+                                         const int* row_kvlen, int M, int H, int t_max, int n_slots, float scale,
+                                         const void* wo_sh, int N, int nt, float* part, int ldp,
+                                         long long split_stride, hipStream_t stream) {
     if (M < 1 || M > 4 || H < 1 || t_max < 1 || N % 16 || nt < 1 || (N / 16) % nt) return hipErrorInvalidValue;
     const float sl2 = scale * 1.4426950408889634f;
     const dim3 grid(H, (N / 16) / nt);
@@ -1523,15 +1621,31 @@ extern "C" hipError_t dlms_attention_oproj(const void* q, int ldq, const void* k
                            ldp, split_stride);
     };
     switch (nt) {
-        case 2: go(attn_oproj_kernel<2>); break;
-        case 3: go(attn_oproj_kernel<3>); break;
-        case 4: go(attn_oproj_kernel<4>); break;
-        case 5: go(attn_oproj_kernel<5>); break;
-        case 6: go(attn_oproj_kernel<6>); break;
-        case 8: go(attn_oproj_kernel<8>); break;
+        case 2: go(attn_oproj_kernel<2, KV8>); break;
+        case 3: go(attn_oproj_kernel<3, KV8>); break;
+        case 4: go(attn_oproj_kernel<4, KV8>); break;
+        case 5: go(attn_oproj_kernel<5, KV8>); break;
+        case 6: go(attn_oproj_kernel<6, KV8>); break;
+        case 8: go(attn_oproj_kernel<8, KV8>); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_attention_oproj(const void* q, int ldq, const void* kc, const void* vc, const int* row_slot,
+                                           const int* row_kvlen, int M, int H, int t_max, int n_slots, float scale,
+                                           const void* wo_sh, int N, int nt, float* part, int ldp,
+                                           long long split_stride, hipStream_t stream) {
+    return attention_oproj_launch<false>(q, ldq, kc, vc, row_slot, row_kvlen, M, H, t_max, n_slots, scale, wo_sh, N, nt,
+                                         part, ldp, split_stride, stream);
+}
+
+extern "C" hipError_t dlms_attention_oproj_fp8(const void* q, int ldq, const void* kc, const void* vc,
+                                               const int* row_slot, const int* row_kvlen, int M, int H, int t_max,
+                                               int n_slots, float scale, const void* wo_sh, int N, int nt, float* part,
+                                               int ldp, long long split_stride, hipStream_t stream) {
+    return attention_oproj_launch<true>(q, ldq, kc, vc, row_slot, row_kvlen, M, H, t_max, n_slots, scale, wo_sh, N, nt,
+                                        part, ldp, split_stride, stream);
 }
 
 DLMS_CHECK_EXPORT(skinny)

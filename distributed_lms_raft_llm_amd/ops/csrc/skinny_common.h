@@ -8,7 +8,9 @@
 
 // SK_FIXADD: like SK_F32 (x += acc + bias, column-owning, in place) into copy 0 of the int64
 // fixed-point residual the fused MLP accumulates (see DLMS_FIX_SCALE below)
-enum { SK_BF16 = 0, SK_GELU_TANH = 1, SK_F32 = 3, SK_QKV = 4, SK_ARGMAX = 5, SK_PARTIAL = 6, SK_FIXADD = 7 };
+// SK_QKV8: SK_QKV into the fp8 (e4m3) KV cache -- a template mode of the kernels like gemm.hip's KV8,
+// selected by the launchers from GemmEpi::kv_fp8 (callers pass SK_QKV); q is written as in SK_QKV
+enum { SK_BF16 = 0, SK_GELU_TANH = 1, SK_F32 = 3, SK_QKV = 4, SK_ARGMAX = 5, SK_PARTIAL = 6, SK_FIXADD = 7, SK_QKV8 = 8 };
 
 // A fragment of rows [16 mt, 16 mt + 16) at k-block kb from the LDS LayerNorm image
 __device__ __forceinline__ bf16x8_t lds_a_frag(const char* img, int row_bytes, int row, int kb, int g) {
@@ -51,9 +53,14 @@ __device__ __forceinline__ void skinny_store(const f32x4_t* acc, int M, int col,
             }
         return;
     }
-    if constexpr (EPI == SK_QKV) {
+    if constexpr (EPI == SK_QKV || EPI == SK_QKV8) {
         // K/V rows go to each row's cache slot / position: both index loads of every row are issued
-        // before the first store (interleaved with the stores they were one round trip per row)
+        // before the first store (interleaved with the stores they were one round trip per row).
+        // SK_QKV8: the caches are e4m3 byte caches [slot][H][T][64] (64-B key rows); the value is the
+        // bf16 the bf16 cache would hold, clamped and rounded to nearest-even e4m3
+        // (models/gpt2.py quantize_kv_e4m3; the clamp keeps the NaN byte out).  A wave's 16 adjacent
+        // columns are 16 adjacent bytes of one key row: one byte store per lane where the bf16 cache
+        // takes one 2-byte store, the same instruction count.
         const int part = col / ep.d_local;
         const int within = col - part * ep.d_local;
         if (part == 0) {
@@ -86,7 +93,13 @@ __device__ __forceinline__ void skinny_store(const f32x4_t* acc, int M, int col,
                 if (row >= M) continue;
                 const size_t slot = dlms_idx(sl[t][r], ep.n_slots, CHK_QKV_SLOT);
                 const size_t pos = dlms_idx(ps[t][r], ep.t_max, CHK_QKV_POS);
-                cache[((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim] = f32_to_bf16(acc[t][r] + bv);
+                if constexpr (EPI == SK_QKV8) {
+                    const float cv = e4m3_clamp(bf16_to_f32(f32_to_bf16(acc[t][r] + bv)));
+                    reinterpret_cast<unsigned char*>(cache)[((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim] =
+                        (unsigned char)__builtin_amdgcn_cvt_pk_fp8_f32(cv, cv, 0, false);
+                } else {
+                    cache[((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim] = f32_to_bf16(acc[t][r] + bv);
+                }
             }
         return;
     }

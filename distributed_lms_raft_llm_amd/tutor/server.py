@@ -158,10 +158,12 @@ class TutoringServicer:
 
 
 def make_engine(model: str, device: str, max_batch: int, max_length: int, weights: str | None = None, seed: int = 0,
-                tp_group=None, weight_dtype: str = "bf16", kv_dtype: str = "bf16"):
+                tp_group=None, weight_dtype: str = "bf16", kv_dtype: str = "bf16", latency_path: bool | None = None):
     """GPU: the HIP engine (TP over ``tp_group`` when given).  CPU: the torch reference engine, or
     the sharded torch slot engine when a (gloo) TP group is given.  ``kv_dtype="fp8"``: the e4m3 KV
-    cache (HIP engine) or its reference model (torch engine); not with a TP group."""
+    cache (HIP engine) or its reference model (torch engine); not with a TP group.  ``latency_path``
+    goes to the HIP engine as it is (None: its default; True also turns the low-batch paths on over
+    an fp8 cache); the torch engines have no such paths and ignore it."""
     if kv_dtype == "fp8" and tp_group is not None:
         from ..engine.gpt2_engine import kv_fp8_unsupported
 
@@ -174,7 +176,7 @@ def make_engine(model: str, device: str, max_batch: int, max_length: int, weight
         from ..engine.gpt2_engine import HipGPT2Engine
 
         return HipGPT2Engine(cfg, w, device=device, max_batch=max_batch, max_length=max_length, tp_group=tp_group,
-                             weight_dtype=weight_dtype, kv_dtype=kv_dtype)
+                             weight_dtype=weight_dtype, kv_dtype=kv_dtype, latency_path=latency_path)
     if tp_group is not None:
         from ..parallel.tp import TorchSlotEngine
 
@@ -451,6 +453,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the KV cache holds e4m3 bytes without scales -- half the bytes the decode attention "
                          "streams, twice the slots in the same HBM, reduced precision; one GPU per replica, bf16 weights")
+    ap.add_argument("--latency-path", choices=("auto", "on", "off"), default="auto",
+                    help="the GPU engine's low-batch decode paths (latency / mid-batch steps): auto = the engine's "
+                         "default (on with the bf16 KV cache, off with --kv-dtype fp8), on / off force them -- on "
+                         "also with --kv-dtype fp8")
     ap.add_argument("--tp", type=int, default=0, help="tensor-parallel degree under torchrun (default: world)")
     ap.add_argument("--batching", choices=("auto", "continuous", "window"), default="auto")
     ap.add_argument("--chunk", type=int, default=8, help="decode steps between scheduler polls")
@@ -541,7 +547,8 @@ def main(argv=None):
         src = dp_idx * tp
         device = f"cuda:{local}" if args.device != "cpu" and torch.cuda.is_available() else "cpu"
         eng = make_engine(args.model, device, args.max_batch, args.max_length, args.weights, tp_group=tp_group,
-                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
+                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype,
+                          latency_path={"auto": None, "on": True, "off": False}[args.latency_path])
         if rank != src:
             n = serve_follower(eng, ctrl, src)
             log.info("TP follower rank %d done after %d commands", rank, n)
@@ -552,7 +559,8 @@ def main(argv=None):
         args.port += dp_idx
     else:
         eng = make_engine(args.model, args.device, args.max_batch, args.max_length, args.weights,
-                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
+                          weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype,
+                          latency_path={"auto": None, "on": True, "off": False}[args.latency_path])
     args.max_batch = getattr(eng, "max_batch", 0) or args.max_batch or 64
     if args.warm_batch > 0 and hasattr(eng, "warm_decode_graphs"):
         # (a TP proxy mirrors the call to every rank of its group: the captures' warm-up steps run

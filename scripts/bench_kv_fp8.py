@@ -11,6 +11,14 @@ engines' greedy tokens agree -- one JSON line per point:
 persistent grid of the overlapped step) at 512 rows x 12 heads, kvlen 150 and 1024, bf16 against
 fp8 cache, in us and achieved TB/s of K/V bytes; the caches rotate over enough copies to stay out
 of the 256 MB last-level cache, as the 12 layers of a decode step do.
+
+``--latency``: the low-batch end instead -- 1, 2, 8, 32 and 64 concurrent queries (32 -> 150, greedy,
+penalty 1.2), three engines of one config alternating in one process: the fp8 cache on the tiled
+step (the default), the fp8 cache with ``latency_path=True`` (latency / mid-batch steps), and the
+bf16 cache with the one-row dataflow decode off (``DLMS_DATAFLOW=0``), so that like is compared with
+like; ms per generation as median (min ... max) of ``--runs``.  Then the three attention kernels of
+those paths alone (split attention at 1 x 12 and 32 x 12 pairs, the fused attention +
+out-projection and its head-grouped variant at one row), kvlen 150 and 1024, fp8 against bf16.
 """
 from __future__ import annotations
 
@@ -130,13 +138,133 @@ def bench_kernels(iters: int) -> list[dict]:
     return lines
 
 
+LATENCY_QUERIES = (1, 2, 8, 32, 64)
+
+
+def bench_latency_point(queries: int, runs: int, max_length: int = 150) -> dict:
+    import torch
+
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine
+    from distributed_lms_raft_llm_amd.models.config import gpt2_config
+    from distributed_lms_raft_llm_amd.models.gpt2 import init_gpt2_weights
+
+    cfg = gpt2_config("gpt2")
+    w = init_gpt2_weights(cfg, seed=0)
+    g = torch.Generator().manual_seed(1)
+    prompts = torch.randint(0, cfg.vocab_size - 1, (queries, PROMPT_LEN), generator=g).tolist()
+    kw = dict(max_batch=max(8, queries), max_length=max_length)
+    engines = {"fp8_tiled": HipGPT2Engine(cfg, w, kv_dtype="fp8", **kw),
+               "fp8_latency": HipGPT2Engine(cfg, w, kv_dtype="fp8", latency_path=True, **kw)}
+    df = os.environ.get("DLMS_DATAFLOW")
+    os.environ["DLMS_DATAFLOW"] = "0"  # read by the constructor: the bf16 engine runs launch-per-op at one row too
+    try:
+        engines["bf16_latency"] = HipGPT2Engine(cfg, w, **kw)
+    finally:
+        if df is None:
+            del os.environ["DLMS_DATAFLOW"]
+        else:
+            os.environ["DLMS_DATAFLOW"] = df
+    assert not any(e.dataflow for e in engines.values())
+    paths = {k: ("latency" if e._small_ok(queries) else "mid" if e._mid_ok(queries) else "tiled")
+             for k, e in engines.items()}
+    outs = {k: timed(e, prompts)[0] for k, e in engines.items()}  # decode graph captures
+    for k, e in engines.items():  # ... and the prefill graph, captured when a shape is seen again
+        assert timed(e, prompts)[0] == outs[k]
+    res = {k: {"ms": [], "decode_ms": []} for k in engines}
+    for _ in range(runs):
+        for k, eng in engines.items():
+            out, ms, dec, _ = timed(eng, prompts)
+            assert out == outs[k], "greedy generation is not reproducible"
+            res[k]["ms"].append(ms)
+            res[k]["decode_ms"].append(dec)
+    same = total = 0
+    for a, b in zip(outs["fp8_tiled"], outs["fp8_latency"]):
+        total += max(len(a), len(b)) - PROMPT_LEN
+        same += sum(x == y for x, y in zip(a[PROMPT_LEN:], b[PROMPT_LEN:]))
+    line = {"point": f"latency_q{queries}", "queries": queries, "prompt_len": PROMPT_LEN, "max_length": max_length,
+            "runs": runs, "paths": paths, "fp8_token_agreement_tiled_vs_latency": round(same / max(1, total), 4)}
+    for k in engines:
+        line[k] = {m: spread(v) for m, v in res[k].items()}
+    t, lat = line["fp8_tiled"]["ms"], line["fp8_latency"]["ms"]
+    line["fp8_latency_over_tiled_ms"] = round(lat["median"] / t["median"], 4)
+    # the dispatch rule: the latency / mid step may be slower than the tiled step of the same tree by
+    # at most this point's own run-to-run spread (max - min of the runs)
+    line["fp8_latency_slower_by_ms"] = round(lat["median"] - t["median"], 3)
+    line["spread_ms"] = round(max(t["max"] - t["min"], lat["max"] - lat["min"]), 3)
+    for e in engines.values():
+        e.close()
+    return line
+
+
+def bench_latency_kernels(iters: int) -> list[dict]:
+    import torch
+
+    from distributed_lms_raft_llm_amd import ops
+
+    dev, H, S = "cuda", 12, 32
+    d = H * 64
+    lines = []
+    wo_sh = ops.shuffle_weight((torch.randn(d, d, device=dev) * 0.05).bfloat16())
+    for kvlen in (150, 1024):
+        copies = 12  # one cache per layer of a decode step
+        caches = {"bf16": [], "fp8": []}
+        for _ in range(copies):
+            k = torch.randn(S, H, kvlen, 64, device=dev).bfloat16()
+            v = torch.randn(S, H, kvlen, 64, device=dev).bfloat16()
+            caches["bf16"].append((k, v))
+            caches["fp8"].append((k.to(ops.FP8), v.to(ops.FP8)))
+        for rows in (1, 32):
+            q = torch.randn(rows, d, device=dev).bfloat16()
+            slot = torch.randperm(S, device=dev)[:rows].to(torch.int32)
+            kvl = torch.full((rows,), kvlen, dtype=torch.int32, device=dev)
+            out = torch.empty(rows, d, dtype=torch.bfloat16, device=dev)
+            nw, ns = ops.attention_split_geometry(rows * H, kvlen)
+            ws = ops.AttnSplitWorkspace(rows * H, ns, dev) if ns > 1 else None
+            parts = torch.zeros(H, 4, d, device=dev)
+            kernels = {"attention_split": lambda k, v: ops.attention_split(q, k, v, slot, kvl, out=out, waves=nw,
+                                                                         splits=ns, workspace=ws)}
+            if rows == 1:
+                kernels["attention_oproj"] = lambda k, v: ops.attention_oproj(q, k, v, slot, kvl, wo_sh, parts)
+                kernels["attention_oproj_grouped"] = lambda k, v: ops.attention_oproj_grouped(q, k, v, slot, kvl, wo_sh,
+                                                                                              parts, 3, tiles=3)
+            for name, fn in kernels.items():
+                for kv in ("bf16", "fp8"):
+                    def run(n):
+                        for i in range(n):
+                            fn(*caches[kv][i % copies])
+                    run(copies)
+                    us = []
+                    for _ in range(5):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        run(iters)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        us.append(e0.elapsed_time(e1) * 1e3 / iters)
+                    lines.append({"kernel": name, "kv_dtype": kv, "rows": rows, "heads": H, "kvlen": kvlen,
+                                  "waves": nw if name == "attention_split" else 4,
+                                  "splits": ns if name == "attention_split" else 1, "us": spread(us)})
+        del caches
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--points", nargs="+", default=list(POINTS), choices=list(POINTS))
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=48)
+    ap.add_argument("--latency", action="store_true",
+                    help="the low-batch points (fp8 tiled / fp8 latency + mid / bf16) and their attention kernels instead")
+    ap.add_argument("--latency-queries", nargs="+", type=int, default=list(LATENCY_QUERIES))
     args = ap.parse_args()
+    if args.latency:
+        for n in args.latency_queries:
+            print(json.dumps(bench_latency_point(n, args.runs)), flush=True)
+        if args.kernels:
+            for line in bench_latency_kernels(args.kernel_iters):
+                print(json.dumps(line), flush=True)
+        return
     for p in args.points:
         print(json.dumps(bench_point(p, args.runs)), flush=True)
     if args.kernels:
