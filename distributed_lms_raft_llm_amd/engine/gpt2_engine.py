@@ -193,6 +193,55 @@ def kv_fp8_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
     return None
 
 
+def prefix_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
+    """Why an engine of this shape cannot keep a prompt-prefix cache (None: it can)."""
+    if tp_size > 1:
+        return ("the prompt-prefix cache is not supported with tensor parallelism (tp_size > 1): the prefix store "
+                "and its fill are built for one rank's whole cache; serve prefix_capacity=0 or TP=1")
+    if fp8_weights:
+        return ("the prompt-prefix cache is not supported with fp8 weights: the suffix-only prefill is verified on "
+                "the bf16 GEMMs only; serve prefix_capacity=0 or weight_dtype='bf16'")
+    return None
+
+
+def split_prefix(prompts, prefix) -> list[int]:
+    """Per prompt, the number of leading tokens the prefix cache supplies: ``len(prefix)`` when the
+    prompt starts with ``prefix`` and is longer than it (at least one suffix row has to run for the
+    first token), else 0 -- a prompt equal to the prefix, a shorter one, or one differing in any
+    prefix token is prefilled whole."""
+    prefix = list(prefix) if prefix is not None else []
+    P = len(prefix)
+    if P == 0:
+        return [0] * len(prompts)
+    return [P if len(p) > P and list(p[:P]) == prefix else 0 for p in prompts]
+
+
+def pack_prompts(prompts, slots, pfx=None):
+    """The packed arrays of a prefill (numpy int64): the tokens, positions and slots of the rows
+    that run -- prompt i without its first ``pfx[i]`` tokens (``split_prefix``; None: whole prompts),
+    positions starting at ``pfx[i]`` -- then per prompt the index of its last row, its full length
+    and the length of its suffix (what ``ops.AttnTiles`` is built from).
+    Returns (tokens, positions, row slots, last rows, lengths, suffix lengths)."""
+    lens_np = np.asarray([len(p) for p in prompts], dtype=np.int64)
+    if pfx is None or not any(pfx):
+        pfx_np = np.zeros(len(prompts), dtype=np.int64)
+        rows = itertools.chain.from_iterable(prompts)
+    else:
+        pfx_np = np.asarray(pfx, dtype=np.int64)
+        rows = itertools.chain.from_iterable(p[k:] for p, k in zip(prompts, pfx))
+    sl_np = lens_np - pfx_np
+    if sl_np.min() < 1:
+        raise ValueError("prefill: every prompt needs at least one row past its cached prefix")
+    R = int(sl_np.sum())
+    ends = np.cumsum(sl_np)
+    # (numpy, no per-prompt Python loops: a 1024-prompt admission used to spend ~20 ms of host time
+    # here with the GPU idle)
+    tok_np = np.fromiter(rows, dtype=np.int64, count=R)
+    pos_np = np.arange(R, dtype=np.int64) - np.repeat(ends - sl_np - pfx_np, sl_np)
+    slot_np = np.repeat(np.asarray(slots, dtype=np.int64), sl_np)
+    return tok_np, pos_np, slot_np, ends - 1, lens_np, sl_np
+
+
 class HipGPT2Engine:
     # (row, head) pairs up to which decode attention uses the split-K kernel (profiles/r2_skinny_bench.log:
     # at 32 rows x 12 heads, T=150: 7.9 us vs 12.3 us for one wave per pair)
@@ -211,8 +260,14 @@ class HipGPT2Engine:
                  check_every: int = 16, max_batch_cap: int = 4096, weight_dtype: str = "bf16",
                  overlap: bool | None = None, overlap_min_batch: int = 512, overlap_parts: int | None = None,
                  p2p: bool | None = None, latency_path: bool | None = None, prefill_split: int | None = None,
-                 kv_dtype: str = "bf16"):
-        """``kv_dtype="fp8"``: the KV cache holds OCP e4m3 bytes without scales
+                 kv_dtype: str = "bf16", prefix_capacity: int = 0):
+        """``prefix_capacity > 0``: an opt-in prompt-prefix cache of up to that many tokens
+        (``set_prompt_prefix``): the K/V of a token prefix shared by the prompts are computed once and
+        kept in a prefix store; a prompt that starts with it prefills only its suffix rows and gets
+        the prefix's K/V copied into its slot (``ops.kv_prefix_fill``), after which every decode
+        path runs unchanged.  bf16 weights on one GPU (``prefix_unsupported``: ``ValueError``); both
+        KV dtypes.  0 (default): no store, and every launch is the one made without the feature.
+        ``kv_dtype="fp8"``: the KV cache holds OCP e4m3 bytes without scales
         (``models.gpt2.quantize_kv_e4m3``: the bf16 cache's content, saturated and rounded to
         nearest-even e4m3) -- half the bytes the decode attention streams and twice the slots per
         GiB, at reduced precision (the oracle is ``GPT2Reference(kv_dtype="fp8")``).  By default
@@ -250,6 +305,14 @@ class HipGPT2Engine:
             why = kv_fp8_unsupported(2 if tp_group is not None else 1, w8)
             if why:
                 raise ValueError(why)
+        prefix_capacity = int(prefix_capacity)
+        if prefix_capacity < 0:
+            raise ValueError("prefix_capacity: >= 0")
+        if prefix_capacity:
+            w8 = weights.fp8 if isinstance(weights, GPT2DeviceWeights) else weight_dtype == "fp8"
+            why = prefix_unsupported(2 if tp_group is not None else 1, w8)
+            if why:
+                raise ValueError(why)
         if not torch.cuda.is_available():
             raise RuntimeError("HipGPT2Engine needs a GPU (use TorchGPT2Engine on CPU)")
         ops.lib()  # fail loudly if the kernel library is missing
@@ -279,9 +342,20 @@ class HipGPT2Engine:
             from .memory import plan_max_batch
 
             max_batch = plan_max_batch(cfg, max_length, self.tp_size, weights_resident=True, cap=max_batch_cap,
-                                       device=self.device, kv_dtype=kv_dtype)
+                                       device=self.device, kv_dtype=kv_dtype,
+                                       prefix_capacity=min(prefix_capacity, max_length))
         self.max_batch = int(max_batch)
         self.max_length = max_length
+        # prompt-prefix cache (set_prompt_prefix): rows of the store (more than max_length are no use)
+        self.prefix_capacity = min(prefix_capacity, max_length)
+        self._pfx_tokens: list[int] | None = None
+        self.prefix_hits = 0  # prompts admitted with their prefix taken from the store
+        self.prefix_rows_skipped = 0  # prefill rows those prompts did not run
+        self.prefix_prompts = 0  # prompts admitted while a prefix was set (hit rate = hits / prompts)
+        # decode attention launches, issued or captured, that read the shared keys from the store
+        # (wave / persistent kernels on a bf16 cache; every other path reads the slots' copies)
+        self.prefix_decode_launches = 0
+        self.prefix_decode = os.environ.get("DLMS_PREFIX_DECODE", "1") != "0"
         self.use_graph = use_graph
         self.prefill_split = prefill_split
         self.check_every = check_every
@@ -544,10 +618,24 @@ class HipGPT2Engine:
         # and every slot's request stream id (written at admission)
         self.rng_seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.rng_stream = torch.zeros(B, dtype=torch.int64, device=dev)
+        # prompt-prefix cache: the store [L][2][H_local][capacity][64] in the cache's dtype, every
+        # slot's count of leading keys that came from it, and the prefix's tokens and seen-bitmap
+        # row -- all at fixed addresses for the engine's life, so captured prefills stay valid when
+        # the prefix is replaced
+        self.pfx_store = self.slot_pfx = self._pfx_tok_d = self._pfx_seen = None
+        if self.prefix_capacity:
+            C = self.prefix_capacity
+            self.pfx_store = torch.zeros(cfg.n_layer, 2, Hl, C, 64, dtype=self.kv.dtype, device=dev)
+            self.slot_pfx = torch.zeros(B, dtype=i32, device=dev)
+            self._pfx_tok_d = torch.zeros(C, dtype=i32, device=dev)
+            self._pfx_seen = torch.zeros(self.seen_words, dtype=i32, device=dev)
         self._reset_slots(0, B)
 
     def kv_cache_bytes(self) -> int:
-        return self.kv.numel() * self.kv.element_size()
+        n = self.kv.numel() * self.kv.element_size()
+        if self.pfx_store is not None:
+            n += self.pfx_store.numel() * self.pfx_store.element_size()
+        return n
 
     # ------------------------------------------------------------------ collectives
     def _all_reduce(self, t: torch.Tensor):
@@ -689,9 +777,22 @@ class HipGPT2Engine:
         elif r.persist_attn:
             # overlapped step: a fixed low-occupancy grid leaves wave slots to the other half's GEMMs
             ops.row_attention(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, out=r.att,
-                              impl="persist", blocks=self.persist_attn_blocks)
+                              impl="persist", blocks=self.persist_attn_blocks, prefix=self._attn_prefix(li))
         else:  # decode (K5): one query per sequence, a pure KV stream
-            ops.row_attention(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, out=r.att)
+            ops.row_attention(r.q, self.kv[li, 0], self.kv[li, 1], r.row_slot, r.row_kvlen, out=r.att,
+                              prefix=self._attn_prefix(li))
+
+    def _pfx_decode(self) -> bool:
+        """The wave / persistent decode attention reads the slots' shared leading keys from the
+        prefix store (a prefix is set, bf16 cache; ``DLMS_PREFIX_DECODE=0``: from the slots, which
+        hold the same bytes -- the A/B switch of scripts/bench_prefix.py)."""
+        return self._pfx_tokens is not None and not self.kv_fp8 and self.prefix_decode
+
+    def _attn_prefix(self, li: int):
+        if not self._pfx_decode():
+            return None
+        self.prefix_decode_launches += 1  # (issued or captured: a graph replay does not count again)
+        return self.pfx_store[li, 0], self.pfx_store[li, 1], self.slot_pfx
 
     def _attn_out_mlp(self, r: "_Rows", li: int):
         """out-proj -> LN2 -> c_fc + GELU -> c_proj; leaves c_proj's residual update pending."""
@@ -840,7 +941,10 @@ class HipGPT2Engine:
         return list(range(first, first + n))
 
     def _skey(self) -> tuple:
-        return () if self._sampling is None else self._sampling.shape_key
+        """What the captured graphs depend on beyond their shapes: the sampling mode, and whether the
+        decode attention reads the prefix store."""
+        key = () if self._sampling is None else self._sampling.shape_key
+        return key + ("pfx",) if self._pfx_decode() else key
 
     def _overlap_ok(self, B: int) -> bool:
         k = self.overlap_parts
@@ -1207,6 +1311,48 @@ class HipGPT2Engine:
         self.cur_tok[lo:hi].fill_(self.cfg.eos_token_id)
         self.cur_pos[lo:hi].zero_()
         self.cur_kvlen[lo:hi].fill_(1)
+        if self.slot_pfx is not None:
+            self.slot_pfx[lo:hi].zero_()
+
+    # ------------------------------------------------------------------ prompt-prefix cache
+    @torch.no_grad()
+    def set_prompt_prefix(self, tokens):
+        """Set (``tokens``: 1 .. min(prefix_capacity, max_length - 2) ids), replace or clear (None)
+        the shared prompt prefix.  Its K/V are computed once, by the ordinary packed prefill of
+        ``tokens`` as one prompt into slot 0 (the layers only: no LM head, no first token, no
+        bookkeeping), and copied into the prefix store; from then on a prompt that starts with
+        ``tokens`` and is longer (``split_prefix``) prefills only its suffix.  The engine matches per
+        prompt, so any other prompt is served as before.  ``RuntimeError`` while any slot is
+        unfinished: its decode may be reading the store."""
+        if not self.prefix_capacity:
+            raise ValueError("set_prompt_prefix: the engine was built with prefix_capacity=0")
+        if int(self.finished.min().item()) == 0:
+            raise RuntimeError("set_prompt_prefix: a slot is unfinished; change the prefix between batches")
+        self.slot_pfx.zero_()  # (every slot is finished: none counts on the old store any more)
+        if tokens is None:
+            self._pfx_tokens = None
+            return
+        toks = [int(t) for t in tokens]
+        P, cap = len(toks), min(self.prefix_capacity, self.max_length - 2)
+        if not 1 <= P <= cap:
+            raise ValueError(f"set_prompt_prefix: 1 .. {cap} tokens (prefix_capacity, max_length - 2), got {P}")
+        if min(toks) < 0 or max(toks) >= self.cfg.vocab_size:
+            raise ValueError("set_prompt_prefix: token id out of range")
+        self._pfx_tokens = None  # (not valid until the store is written)
+        dev = self.device
+        tok_np, pos_np, slot_np, _, _, sl_np = pack_prompts([toks], [0])
+        tokens_d, pos_d, slot_d = (_to_device(a, dev) for a in (tok_np, pos_np, slot_np))
+        self._prefill_layers(tokens_d, pos_d, slot_d, ops.AttnTiles(sl_np.tolist(), dev))
+        self.pfx_store[:, :, :, :P].copy_(self.kv[:, :, 0, :, :P])
+        self._pfx_tok_d.zero_()
+        self._pfx_tok_d[:P].copy_(tokens_d)
+        self._pfx_seen.copy_(_to_device(seen_bitmap(toks, self.seen_words), dev))
+        self._pfx_tokens = toks
+
+    @property
+    def prompt_prefix(self) -> list[int] | None:
+        """The tokens of the prefix in the store (None: no prefix set)."""
+        return None if self._pfx_tokens is None else list(self._pfx_tokens)
 
     def _prefill_into(self, prompts: list[list[int]], slots: list[int], penalty: float,
                       streams: list[int] | None = None):
@@ -1224,16 +1370,25 @@ class HipGPT2Engine:
         lens = [len(p) for p in prompts]
         if min(lens) < 1 or max(lens) > T:
             raise ValueError("prefill: prompt lengths must be in [1, max_length]")
-        R = sum(lens)
-        # packed token / position / slot arrays built with numpy (no per-prompt Python loops: a
-        # 1024-prompt admission used to spend ~20 ms of host time here with the GPU idle)
-        lens_np = np.asarray(lens, dtype=np.int64)
-        ends = np.cumsum(lens_np)
-        tok_np = np.fromiter(itertools.chain.from_iterable(prompts), dtype=np.int64, count=R)
+        # prompt-prefix cache: the prompts that start with the stored prefix run their suffix rows
+        # only (one packed prefill with the others); pfx_np is None on an engine without a store
+        pfx = pfx_np = None
+        if self.prefix_capacity:
+            pfx = split_prefix(prompts, self._pfx_tokens)
+            pfx_np = np.asarray(pfx, dtype=np.int64)
+            if self._pfx_tokens is not None:
+                hits, rows = sum(1 for k in pfx if k), sum(pfx)
+                self.prefix_prompts += n
+                self.prefix_hits += hits
+                self.prefix_rows_skipped += rows
+                METRICS.inc("engine_prefix_prompts", n)
+                METRICS.inc("engine_prefix_hits", hits)
+                METRICS.inc("engine_prefix_rows_skipped", rows)
+        # packed token / position / slot arrays built with numpy (pack_prompts)
+        tok_np, pos_np, slot_np, last_np, lens_np, sl_np = pack_prompts(prompts, slots, pfx)
+        R = tok_np.size
         if tok_np.min() < 0 or tok_np.max() >= cfg.vocab_size:
             raise ValueError("prefill: token id out of range")
-        pos_np = np.arange(R, dtype=np.int64) - np.repeat(ends - lens_np, lens_np)
-        slot_np = np.repeat(np.asarray(slots, dtype=np.int64), lens_np)
         if self._sampling is not None:
             # the slots' stream ids, ahead of (and outside) a replayed prefill graph
             if streams is None or len(streams) != n:
@@ -1241,28 +1396,59 @@ class HipGPT2Engine:
             self.rng_stream.index_copy_(0, _to_device(np.asarray(slots), dev, np.int64),
                                         _to_device(np.asarray(streams, dtype=np.uint64).view(np.int64), dev, np.int64))
         if self._prefill_graph_ok(R, n):
-            return self._prefill_graphed(tok_np, pos_np, slot_np, ends - 1, np.asarray(slots), lens_np, penalty)
+            return self._prefill_graphed(tok_np, pos_np, slot_np, last_np, np.asarray(slots), lens_np, penalty, pfx_np)
         tokens_d, pos_d, slot_d, last_d, slots_d, lens_d = (
-            _to_device(a, dev) for a in (tok_np, pos_np, slot_np, ends - 1, np.asarray(slots), lens_np))
-        self._prefill_core(tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, ops.AttnTiles(lens, dev), penalty)
+            _to_device(a, dev) for a in (tok_np, pos_np, slot_np, last_np, np.asarray(slots), lens_np))
+        pfx_d = None if pfx_np is None else _to_device(pfx_np, dev)
+        self._prefill_core(tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, ops.AttnTiles(sl_np.tolist(), dev),
+                           penalty, pfx_d)
 
-    def _prefill_core(self, tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty: float):
-        """Device side of a packed prefill (no host synchronisation: also captured as a graph)."""
-        cfg, dev = self.cfg, self.device
+    def _prefill_core(self, tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty: float, pfx_d=None):
+        """Device side of a packed prefill (no host synchronisation: also captured as a graph).
+        ``pfx_d`` (engines with a prefix store): per prompt the number of leading tokens whose K/V
+        come from the store -- the packed rows are then the suffixes (positions from ``pfx``), the
+        bookkeeping still sees whole prompts, and the store's rows are copied into the slots."""
+        cfg = self.cfg
         T = self.max_length
-        R, n = tokens_d.numel(), slots_d.numel()
+        n = slots_d.numel()
         fin_d = (lens_d >= T).to(torch.int32)
         # per-sequence state scattered into the chosen slots on the device
         idx = slots_d.long()
-        self.out_tokens.index_fill_(0, idx, 0)
-        self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
-        self.seen.index_fill_(0, idx, 0)
+        if pfx_d is None:
+            self.out_tokens.index_fill_(0, idx, 0)
+            self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
+            self.seen.index_fill_(0, idx, 0)
+        else:
+            # the prefix's tokens and seen-bitmap row for the prompts that share it, zeros for the
+            # others; the store's K/V into the slots in one launch, ahead of layer 0
+            C = self.prefix_capacity
+            share = pfx_d[:, None] > torch.arange(C, dtype=torch.int32, device=self.device)[None, :]
+            self.out_tokens.index_fill_(0, idx, 0)
+            self.out_tokens[:, :C].index_copy_(0, idx, self._pfx_tok_d[None, :] * share)
+            self.seen.index_copy_(0, idx, self._pfx_seen[None, :] * (pfx_d[:, None] > 0))
+            self.slot_pfx.index_copy_(0, idx, pfx_d)
+            ops.kv_prefix_fill(self.kv, self.pfx_store, slots_d, pfx_d)
+            self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
         ops.seen_set(self.seen, slot_d, tokens_d)
         self.lens.index_copy_(0, idx, lens_d)
         self.finished.index_copy_(0, idx, fin_d)
         # the LM head of the first token reads the prompts' bitmaps as rows [0, n)
         seen_d = self.seen.index_select(0, idx)
+        x = self._prefill_layers(tokens_d, pos_d, slot_d, tiles)
+        hl = ops.layernorm_gather(x, last_d, self.w.lnf_g, self.w.lnf_b, cfg.layer_norm_epsilon)
+        hsc_l = None
+        if self.w.fp8:
+            hl8 = torch.zeros(n, self.w.k_fp8, dtype=ops.FP8, device=self.device)  # K padding stays zero
+            _, hsc_l = ops.quantize_fp8_rows(hl, out=hl8)
+            hl = hl8
+        # first token: argmax rows are prompts (seen rows gathered), updates land in their slots
+        self._lm_head_and_update(hl, n, penalty, seen=seen_d, hscale=hsc_l, slot_map=slots_d)
 
+    def _prefill_layers(self, tokens_d, pos_d, slot_d, tiles) -> torch.Tensor:
+        """Embedding and every block of a packed prefill (K/V scattered into the rows' slots at
+        their positions); returns the final residual rows, ahead of ln_f."""
+        cfg, dev = self.cfg, self.device
+        R = tokens_d.numel()
         D, Dl, Fl = cfg.n_embd, self.w.d_local, self.w.ffn_local
         f32, bf = torch.float32, torch.bfloat16
         x = ops.embed(tokens_d, pos_d, self.w.wte, self.w.wpe)
@@ -1278,14 +1464,7 @@ class HipGPT2Engine:
             h8 = torch.zeros(R, self.w.k_fp8, dtype=ops.FP8, device=dev)  # K padding stays zero
             hsc = torch.empty(R, dtype=f32, device=dev)
         self._layers(x, parts, h, q, att, ff, slot_d, pos_d, pos_d + 1, R, final_h=None, h8=h8, hsc=hsc, tiles=tiles)
-        hl = ops.layernorm_gather(x, last_d, self.w.lnf_g, self.w.lnf_b, cfg.layer_norm_epsilon)
-        hsc_l = None
-        if self.w.fp8:
-            hl8 = torch.zeros(n, self.w.k_fp8, dtype=ops.FP8, device=dev)  # K padding stays zero
-            _, hsc_l = ops.quantize_fp8_rows(hl, out=hl8)
-            hl = hl8
-        # first token: argmax rows are prompts (seen rows gathered), updates land in their slots
-        self._lm_head_and_update(hl, n, penalty, seen=seen_d, hscale=hsc_l, slot_map=slots_d)
+        return x
 
     # hipGraph-replayed prefill, keyed by (packed rows, prompts): a (rows, prompts) shape seen
     # twice is captured (inputs go through one static pinned -> device buffer, the tile table is
@@ -1315,13 +1494,18 @@ class HipGPT2Engine:
             return False
         return R * self.cfg.n_embd * 4 <= self.xgmi.slab_bytes or dist.get_backend(self.tp_group) == "nccl"
 
-    def _prefill_graphed(self, tok, pos, slot, last, slots, lens, penalty: float):
+    def _prefill_graphed(self, tok, pos, slot, last, slots, lens, penalty: float, pfx=None):
+        """``pfx`` (engines with a prefix store): per prompt the leading tokens taken from the store;
+        the packed rows and the tiles are then those of the suffixes, and ``pfx`` is staged with the
+        other per-prompt words (one graph serves every mix of sharing and other prompts of its
+        (rows, prompts) shape)."""
         R, n = tok.size, slots.size
         key = (R, n) + self._skey()
         TB = R // 16 + n  # >= the tile count of any R rows in n prompts
+        npp = 3 if pfx is None else 4  # staged words per prompt
         st = self._pgraphs.get(key)
         if st is None:
-            words = 3 * R + 3 * n + 2 * TB
+            words = 3 * R + npp * n + 2 * TB
             st = dict(host=torch.empty(words, dtype=torch.int32).pin_memory(),
                       dev=torch.empty(words, dtype=torch.int32, device=self.device), copied=torch.cuda.Event(),
                       graph=None, penalty=penalty)
@@ -1331,23 +1515,27 @@ class HipGPT2Engine:
         hbuf[:R], hbuf[R:2 * R], hbuf[2 * R:3 * R] = tok, pos, slot
         o = 3 * R
         hbuf[o:o + n], hbuf[o + n:o + 2 * n], hbuf[o + 2 * n:o + 3 * n] = last, slots, lens
-        nt = (lens + 15) // 16
+        rl = lens  # rows each prompt runs: its suffix
+        if pfx is not None:
+            hbuf[o + 3 * n:o + 4 * n] = pfx
+            rl = lens - pfx
+        nt = (rl + 15) // 16
         seq = np.repeat(np.arange(n), nt)
         k = np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)
-        starts = np.cumsum(lens) - lens
+        starts = np.cumsum(rl) - rl
         tt = np.empty((TB, 2), dtype=np.int64)
         tt[: len(seq), 0] = starts[seq] + 16 * k
-        tt[: len(seq), 1] = np.minimum(16, lens[seq] - 16 * k)
+        tt[: len(seq), 1] = np.minimum(16, rl[seq] - 16 * k)
         tt[len(seq):] = tt[len(seq) - 1]  # padding tiles repeat the last one (identical writes)
-        hbuf[o + 3 * n:] = tt.reshape(-1)
+        hbuf[o + npp * n:] = tt.reshape(-1)
         st["dev"].copy_(st["host"], non_blocking=True)
         st["copied"].record()
         if st["graph"] is None or st["penalty"] != penalty:
             d = st["dev"]
             tiles = ops.AttnTiles.__new__(ops.AttnTiles)
-            tiles.rows, tiles.n, tiles.t = R, TB, d[o + 3 * n:].view(TB, 2)
+            tiles.rows, tiles.n, tiles.t = R, TB, d[o + npp * n:].view(TB, 2)
             args = (d[:R], d[R:2 * R], d[2 * R:3 * R], d[o:o + n], d[o + n:o + 2 * n], d[o + 2 * n:o + 3 * n], tiles,
-                    penalty)
+                    penalty, None if pfx is None else d[o + 3 * n:o + 4 * n])
             g = torch.cuda.CUDAGraph()
             with capture_guard(), torch.cuda.graph(g):
                 self._prefill_core(*args)
@@ -1474,6 +1662,10 @@ class HipGPT2Engine:
         self._graphs.clear()
         self._pgraphs.clear()
         self._df = None
+        # the prefix store and the slots' prefix counts (after the graphs that captured their addresses)
+        self._pfx_tokens = None
+        self.pfx_store = self.slot_pfx = self._pfx_tok_d = self._pfx_seen = None
+        self.prefix_capacity = 0
         if self.xgmi is not None:
             self.xgmi.close()
             self.xgmi = None

@@ -33,6 +33,13 @@ def kv_bytes(cfg: GPT2Config, max_length: int, tp_size: int = 1, tp_rank: int = 
     return cfg.n_layer * 2 * (h1 - h0) * max_length * cfg.head_dim * KV_ELEMENT_BYTES[kv_dtype]
 
 
+def prefix_store_bytes(cfg: GPT2Config, prefix_capacity: int, tp_size: int = 1, tp_rank: int = 0,
+                       kv_dtype: str = "bf16") -> int:
+    """Bytes of the engine's prompt-prefix store (``[L][2][H_local][prefix_capacity][64]`` in the cache's
+    dtype: one slot's KV cache cut to ``prefix_capacity`` keys; GPT-2-small, 64 keys, bf16: 2.25 MiB)."""
+    return kv_bytes(cfg, prefix_capacity, tp_size, tp_rank, kv_dtype) if prefix_capacity > 0 else 0
+
+
 def slot_bytes(cfg: GPT2Config, max_length: int, tp_size: int = 1, tp_rank: int = 0, sampling: bool = False,
                kv_dtype: str = "bf16") -> int:
     """Device bytes one decode slot costs on this rank (KV cache + per-sequence state;
@@ -62,10 +69,11 @@ def weight_bytes(cfg: GPT2Config, tp_size: int = 1) -> int:
 def plan_max_batch(cfg: GPT2Config, max_length: int, tp_size: int = 1, free_bytes: int | None = None,
                    weights_resident: bool = False, reserve_frac: float = 0.08, reserve_bytes: int = 4 * GIB,
                    prefill_tokens: int = 32768, cap: int = 4096, device=None, sampling: bool = False,
-                   kv_dtype: str = "bf16") -> int:
+                   kv_dtype: str = "bf16", prefix_capacity: int = 0) -> int:
     """Largest batch bucket (<= ``cap``) whose slots fit in the free HBM after the reserve
     (``sampling``: slots sized for the sampling mode's logits buffer; ``kv_dtype``: for that KV
-    cache element type -- ``slot_bytes``)."""
+    cache element type -- ``slot_bytes``; ``prefix_capacity``: the prompt-prefix store of that many
+    keys comes out of the budget first, plus 4 bytes per slot for its prefix count)."""
     if free_bytes is None:
         import torch
 
@@ -75,7 +83,8 @@ def plan_max_batch(cfg: GPT2Config, max_length: int, tp_size: int = 1, free_byte
         budget -= weight_bytes(cfg, tp_size)
     # transient prefill activations for ``prefill_tokens`` packed prompt tokens
     budget -= prefill_tokens * (cfg.n_embd * 4 * 9 + cfg.n_inner // tp_size * 2 + cfg.n_embd * 6)
-    per = slot_bytes(cfg, max_length, tp_size, sampling=sampling, kv_dtype=kv_dtype)
+    budget -= prefix_store_bytes(cfg, prefix_capacity, tp_size, kv_dtype=kv_dtype)
+    per = slot_bytes(cfg, max_length, tp_size, sampling=sampling, kv_dtype=kv_dtype) + (4 if prefix_capacity > 0 else 0)
     fit = int(budget // per) if budget > 0 else 0
     best = 0
     for b in BUCKETS:

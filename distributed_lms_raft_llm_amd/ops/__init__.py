@@ -31,7 +31,8 @@ CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "s
 CHECK_SITES = {1: "embed token id", 2: "position id", 3: "decode_update slot_map", 4: "decode_update token id",
                5: "decode_update sequence length", 6: "seen_set row", 7: "QKV scatter slot", 8: "QKV scatter position",
                9: "attention slot", 10: "BERT token id", 11: "seen_set token id", 12: "sampler slot_map",
-               13: "sampled token id"}
+               13: "sampled token id", 14: "prefix fill slot", 15: "prefix fill length",
+               16: "attention prefix length"}
 SOURCES = ["api.hip", "gemm.hip", "norm.hip", "attention.hip", "decode.hip", "encoder.hip", "xgmi.hip", "skinny.hip", "gemm_ps.hip",
            "dataflow.hip", "mid.hip", "sample.hip"]
 ARCH = os.environ.get("DLMS_OFFLOAD_ARCH", "gfx950")
@@ -152,6 +153,7 @@ def _bind(L):
                                I, I, I, I, I, P, P, F, P, I, P],
         "dlms_argmax_reduce": [P, I, ctypes.c_longlong, P, I, P],
         "dlms_seen_set": [P, P, I, P, I, I, P],
+        "dlms_kv_prefix_fill": [P, P, P, P, I, I, I, I, I, I, I, P],
         "dlms_bert_embed_ln": [P, P, P, P, P, P, P, P, P, I, I, F, I, I, P],
         "dlms_mean_pool": [P, P, P, P, I, I, P],
         "dlms_cosine": [P, P, P, I, I, I, F, P],
@@ -175,6 +177,8 @@ def _bind(L):
         "dlms_mid_proj": [P, I, P, P, P, I, I, I, I, I, P],
         "dlms_gemm_ps": [I, P, I, P, I, I, I, I, I, I, I, ctypes.POINTER(GemmEpi), P],
         "dlms_attention_persist": [P, I, P, P, P, P, P, I, I, I, I, I, F, I, P],
+        "dlms_attention_pfx": [P, I, P, P, P, P, I, P, P, P, P, I, I, I, I, I, F, P],
+        "dlms_attention_persist_pfx": [P, I, P, P, P, P, I, P, P, P, P, I, I, I, I, I, F, I, P],
         "dlms_sample_topk_topp": [P, ctypes.c_longlong, P, I, P, P, P, I, P, F, ctypes.c_double, I, ctypes.c_double, I,
                                   P, ctypes.c_longlong, I, P],
         "dlms_philox4x32_10": [P, P, I, P],
@@ -551,12 +555,29 @@ def layernorm_gather(x: torch.Tensor, rows: torch.Tensor, gamma, beta, eps: floa
 
 def row_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, row_slot: torch.Tensor,
                   row_kvlen: torch.Tensor, out: torch.Tensor | None = None, scale: float | None = None,
-                  impl: str = "wave", blocks: int = 512):
+                  impl: str = "wave", blocks: int = 512, prefix=None):
     """q: bf16 [R, H*64]; caches bf16 [slots, H, t_max, 64]; row r attends keys [0, row_kvlen[r]).
     impl "wave": one wave per (row, head), online softmax (default); "lds": block per (row, head),
-    exact two-pass softmax through LDS (t_max <= 2048)."""
+    exact two-pass softmax through LDS (t_max <= 2048).
+    ``prefix=(pk, pv, slot_pfx)`` (impl "wave" / "persist", bf16 cache; ``ValueError`` otherwise): the
+    first ``slot_pfx[slot]`` keys of every slot are read from the prefix store ``pk`` / ``pv``
+    (bf16 [H, capacity, 64], contiguous) instead of the slot -- bit-identical to the call without
+    ``prefix`` on slots that hold the store's rows there.  ``slot_pfx``: int32, one count per slot,
+    0 <= count <= capacity."""
     _req(q, torch.bfloat16, "q", 2)
     kv8 = _kv_dtype(k_cache, v_cache, f"row_attention(impl={impl!r})", fp8_ok=impl in ("wave", "persist"))
+    if prefix is not None:
+        if kv8 or impl not in ("wave", "persist"):
+            raise ValueError("row_attention: prefix= is built for impl 'wave' / 'persist' on a bf16 cache")
+        pk, pv, slot_pfx = prefix
+        _req(pk, torch.bfloat16, "prefix K", 3)
+        _req(pv, torch.bfloat16, "prefix V", 3)
+        _req(slot_pfx, torch.int32, "slot_pfx", 1)
+        if pk.shape != pv.shape or pk.shape[0] != k_cache.shape[1] or pk.shape[2] != 64 or pk.shape[1] < 1 or \
+                not pk.is_contiguous() or not pv.is_contiguous() or pk.data_ptr() % 16 or pv.data_ptr() % 16:
+            raise ValueError("row_attention: prefix K / V must be contiguous bf16 [H, capacity, 64], 16-byte aligned")
+        if slot_pfx.numel() < k_cache.shape[0] or not slot_pfx.is_contiguous():
+            raise ValueError("row_attention: slot_pfx needs one count per cache slot")
     _req(k_cache, FP8 if kv8 else torch.bfloat16, "k_cache", 4)
     _req(v_cache, FP8 if kv8 else torch.bfloat16, "v_cache", 4)
     _req(row_slot, torch.int32, "row_slot", 1)
@@ -584,6 +605,18 @@ def row_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
         _check(lib().dlms_attention_persist_fp8(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot),
                                                 _p(row_kvlen), _p(out), out.stride(0), R, H, T, S, float(sc),
                                                 int(blocks), _stream()), "attention_persist_fp8")
+        return out
+    if prefix is not None:  # the first slot_pfx[slot] keys from the prefix store
+        pk, pv, slot_pfx = prefix
+        if impl == "persist":
+            _check(lib().dlms_attention_persist_pfx(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(pk), _p(pv),
+                                                    pk.shape[1], _p(slot_pfx), _p(row_slot), _p(row_kvlen), _p(out),
+                                                    out.stride(0), R, H, T, S, float(sc), int(blocks), _stream()),
+                   "attention_persist_pfx")
+        else:
+            _check(lib().dlms_attention_pfx(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(pk), _p(pv), pk.shape[1],
+                                            _p(slot_pfx), _p(row_slot), _p(row_kvlen), _p(out), out.stride(0), R, H, T,
+                                            S, float(sc), _stream()), "attention_pfx")
         return out
     if impl == "persist":  # fixed low-occupancy grid looping over (row, head) pairs
         _check(lib().dlms_attention_persist(_p(q), q.stride(0), _p(k_cache), _p(v_cache), _p(row_slot), _p(row_kvlen),
@@ -698,6 +731,33 @@ def seen_set(seen: torch.Tensor, rows: torch.Tensor, tokens: torch.Tensor):
     _check(lib().dlms_seen_set(_p(tokens), _p(rows), R, _p(seen), seen.shape[1], seen.shape[0], _stream()),
            "dlms_seen_set")
     return seen
+
+
+def kv_prefix_fill(kv: torch.Tensor, store: torch.Tensor, slots: torch.Tensor, pfx: torch.Tensor):
+    """Prompt-prefix cache: for every listed slot i with ``pfx[i] > 0`` copy ``store[l, kv, h, :pfx[i]]``
+    to ``kv[l, kv, slots[i], h, :pfx[i]]`` for every layer, K and V, and head -- one launch.  ``kv``:
+    the whole cache [L, 2, slots, H, T, 64], ``store``: [L, 2, H, capacity, 64] of the same dtype (bf16
+    or the fp8 byte cache), both contiguous; ``slots`` / ``pfx``: int32 device arrays (read by the
+    kernel, so the call can be captured), distinct slots, 0 <= pfx <= min(capacity, T)."""
+    if not isinstance(kv, torch.Tensor) or not isinstance(store, torch.Tensor):
+        raise TypeError("kv_prefix_fill: kv and store must be tensors")
+    if kv.dtype not in (torch.bfloat16, FP8) or store.dtype != kv.dtype:
+        raise ValueError(f"kv_prefix_fill: kv is {kv.dtype}, store is {store.dtype}: one cache dtype, bf16 or fp8")
+    _req(kv, kv.dtype, "kv", 6)
+    _req(store, kv.dtype, "store", 5)
+    _req(slots, torch.int32, "slots", 1)
+    _req(pfx, torch.int32, "pfx", 1)
+    L, two, S, H, T, hd = kv.shape
+    if two != 2 or hd != 64 or store.shape[:3] != (L, 2, H) or store.shape[4] != 64 or store.shape[3] < 1:
+        raise ValueError("kv_prefix_fill: kv [L, 2, slots, H, T, 64] and store [L, 2, H, capacity, 64]")
+    if not kv.is_contiguous() or not store.is_contiguous() or kv.data_ptr() % 16 or store.data_ptr() % 16:
+        raise ValueError("kv_prefix_fill: kv and store must be contiguous and 16-byte aligned")
+    n = slots.numel()
+    if n == 0 or pfx.numel() != n or n > 65535 or not slots.is_contiguous() or not pfx.is_contiguous():
+        raise ValueError("kv_prefix_fill: one prefix length per listed slot (1 .. 65535 slots)")
+    _check(lib().dlms_kv_prefix_fill(_p(kv), _p(store), _p(slots), _p(pfx), n, 2 * L, S, H, T, store.shape[3],
+                                     64 * kv.element_size(), _stream()), "dlms_kv_prefix_fill")
+    return kv
 
 
 def decode_update(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok, cur_pos, cur_kvlen, wte, wpe, x,

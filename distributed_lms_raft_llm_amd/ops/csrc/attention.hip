@@ -568,6 +568,249 @@ extern "C" hipError_t dlms_attention_fp8(const void* q, int ldq, const void* kc,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Prompt-prefix builds of attn_wave_kernel<4, true> and attn_persist_kernel<8, true> (bf16 cache):
+// the first slot_pfx[slot] keys of a slot are those of the engine's prefix store
+// (pk / pv: this layer's [H][cap][64]), shared by every row.  A lane whose key index t is below
+// that count takes its 16-byte K and V chunks from the store with ordinary cached loads (a few KiB
+// per head and layer, meant to stay in L2); every other chunk keeps the slot's non-temporal load.
+// Key order, masking, the online softmax and the merges are those of the kernels above, statement
+// for statement, so the output is bit-identical to theirs on a slot that holds the same bytes.
+__device__ __forceinline__ void pfx_load(const bf16_t* K, const bf16_t* V, const bf16_t* PK, const bf16_t* PV, int t,
+                                         int pfx, uint4& kr, uint4& vr) {
+    if (t < pfx) {
+        kr = *reinterpret_cast<const uint4*>(PK + (size_t)t * 64);
+        vr = *reinterpret_cast<const uint4*>(PV + (size_t)t * 64);
+    } else {
+        const u32x4_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(K + (size_t)t * 64));
+        const u32x4_t b = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(V + (size_t)t * 64));
+        kr = make_uint4(a.x, a.y, a.z, a.w);
+        vr = make_uint4(b.x, b.y, b.z, b.w);
+    }
+}
+
+// keys of `slot` that come from the store: its count, never past the store's rows
+__device__ __forceinline__ int pfx_count(const int* __restrict__ slot_pfx, int slot, int cap) {
+    int p = (int)dlms_idx(slot_pfx[slot], cap + 1, CHK_ATTN_PFX);
+    return p < 0 ? 0 : (p > cap ? cap : p);
+}
+
+template <int ATT_UNROLL>
+__global__ __launch_bounds__(256) void attn_wave_pfx_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                            const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+                                                            const bf16_t* __restrict__ pk, const bf16_t* __restrict__ pv,
+                                                            int cap, const int* __restrict__ slot_pfx,
+                                                            const int* __restrict__ row_slot,
+                                                            const int* __restrict__ row_kvlen, bf16_t* out, int ldo,
+                                                            int H, int t_max, int n_slots, float scale_log2) {
+    const int lane = threadIdx.x & 63;
+    const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r = blockIdx.y;
+    if (h >= H) return;
+    const int g = lane >> 3;
+    const int c = lane & 7;
+    const int slot = (int)dlms_idx(row_slot[r], n_slots, CHK_ATTN_SLOT);
+    int kvlen = row_kvlen[r];
+    kvlen = kvlen < 1 ? 1 : (kvlen > t_max ? t_max : kvlen);
+    const int pfx = pfx_count(slot_pfx, slot, cap);
+    const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
+    const bf16_t* K = kc + head_off + c * 8;
+    const bf16_t* V = vc + head_off + c * 8;
+    const bf16_t* PK = pk + (size_t)h * cap * 64 + c * 8;
+    const bf16_t* PV = pv + (size_t)h * cap * 64 + c * 8;
+
+    float qf[8];
+    unpack8(*reinterpret_cast<const uint4*>(q + (size_t)r * ldq + h * 64 + c * 8), qf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[j] *= scale_log2;
+
+    float m = -INFINITY, l = 0.f;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int t0 = 0; t0 < kvlen; t0 += 8 * ATT_UNROLL) {
+        uint4 kr[ATT_UNROLL], vr[ATT_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ATT_UNROLL; ++u) {
+            int t = t0 + u * 8 + g;
+            t = t < kvlen ? t : kvlen - 1;  // clamped (masked below): loads never leave the slot / the store
+            pfx_load(K, V, PK, PV, t, pfx, kr[u], vr[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < ATT_UNROLL; ++u) {
+            float kf[8];
+            unpack8(kr[u], kf);
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += qf[j] * kf[j];
+            s = group8_sum(s);
+            const bool valid = t0 + u * 8 + g < kvlen;
+            if (valid) {
+                const float m_new = fmaxf(m, s);
+                const float corr = exp2f(m - m_new);  // m == -inf -> 0 (acc and l are 0 then)
+                const float p = exp2f(s - m_new);
+                float vf[8];
+                unpack8(vr[u], vf);
+                l = l * corr + p;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = acc[j] * corr + p * vf[j];
+                m = m_new;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+        float mx, my, lx, ly;  // (own, partner) or (lower, upper): the merge is symmetric
+        lane_pair(m, o, mx, my);
+        lane_pair(l, o, lx, ly);
+        const float m_n = fmaxf(mx, my);
+        const float a = mx == -INFINITY ? 0.f : exp2f(mx - m_n);
+        const float b = my == -INFINITY ? 0.f : exp2f(my - m_n);
+        l = lx * a + ly * b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float ax, ay;
+            lane_pair(acc[j], o, ax, ay);
+            acc[j] = ax * a + ay * b;
+        }
+        m = m_n;
+    }
+    if (g == 0) {
+        const float inv = 1.f / l;
+        float o8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o8[j] = acc[j] * inv;
+        *reinterpret_cast<uint4*>(out + (size_t)r * ldo + h * 64 + c * 8) = pack8(o8);
+    }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void attn_persist_pfx_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                               const bf16_t* __restrict__ kc,
+                                                               const bf16_t* __restrict__ vc,
+                                                               const bf16_t* __restrict__ pk,
+                                                               const bf16_t* __restrict__ pv, int cap,
+                                                               const int* __restrict__ slot_pfx,
+                                                               const int* __restrict__ row_slot,
+                                                               const int* __restrict__ row_kvlen, bf16_t* out, int ldo,
+                                                               int R, int H, int t_max, int n_slots,
+                                                               float scale_log2) {
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 3;
+    const int c = lane & 7;
+    const int nwaves = gridDim.x * 4;
+    const int npairs = R * H;
+    for (int pair = blockIdx.x * 4 + (threadIdx.x >> 6); pair < npairs; pair += nwaves) {
+        const int r = pair / H, h = pair - r * H;
+        const int slot = (int)dlms_idx(row_slot[r], n_slots, CHK_ATTN_SLOT);
+        int kvlen = row_kvlen[r];
+        kvlen = kvlen < 1 ? 1 : (kvlen > t_max ? t_max : kvlen);
+        const int pfx = pfx_count(slot_pfx, slot, cap);
+        const size_t head_off = ((size_t)slot * H + h) * t_max * 64;
+        const bf16_t* K = kc + head_off + c * 8;
+        const bf16_t* V = vc + head_off + c * 8;
+        const bf16_t* PK = pk + (size_t)h * cap * 64 + c * 8;
+        const bf16_t* PV = pv + (size_t)h * cap * 64 + c * 8;
+        float qf[8];
+        unpack8(*reinterpret_cast<const uint4*>(q + (size_t)r * ldq + h * 64 + c * 8), qf);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[j] *= scale_log2;
+        float m = -INFINITY, l = 0.f;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int t0 = 0; t0 < kvlen; t0 += 8 * U) {
+            uint4 kr[U], vr[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                int t = t0 + u * 8 + g;
+                t = t < kvlen ? t : kvlen - 1;
+                pfx_load(K, V, PK, PV, t, pfx, kr[u], vr[u]);
+            }
+            float sv[U];
+            float mb = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float kf[8];
+                unpack8(kr[u], kf);
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) s += qf[j] * kf[j];
+                s = group8_sum(s);
+                sv[u] = t0 + u * 8 + g < kvlen ? s : -INFINITY;
+                mb = fmaxf(mb, sv[u]);
+            }
+            if (mb != -INFINITY) {  // else every key of this lane group is past kvlen
+                const float m_new = fmaxf(m, mb);
+                const float corr = exp2f(m - m_new);  // m == -inf -> 0
+                float ps = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] *= corr;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float p = exp2f(sv[u] - m_new);  // masked keys -> 0
+                    float vf[8];
+                    unpack8(vr[u], vf);
+                    ps += p;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[j] += p * vf[j];
+                }
+                l = l * corr + ps;
+                m = m_new;
+            }
+        }
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) {
+            float mx, my, lx, ly;  // (own, partner) or (lower, upper): the merge is symmetric
+            lane_pair(m, o, mx, my);
+            lane_pair(l, o, lx, ly);
+            const float m_n = fmaxf(mx, my);
+            const float a = mx == -INFINITY ? 0.f : exp2f(mx - m_n);
+            const float b = my == -INFINITY ? 0.f : exp2f(my - m_n);
+            l = lx * a + ly * b;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float ax, ay;
+                lane_pair(acc[j], o, ax, ay);
+                acc[j] = ax * a + ay * b;
+            }
+            m = m_n;
+        }
+        if (g == 0) {
+            const float inv = 1.f / l;
+            float o8[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o8[j] = acc[j] * inv;
+            *reinterpret_cast<uint4*>(out + (size_t)r * ldo + h * 64 + c * 8) = pack8(o8);
+        }
+    }
+}
+
+extern "C" hipError_t dlms_attention_pfx(const void* q, int ldq, const void* kc, const void* vc, const void* pk,
+                                         const void* pv, int cap, const int* slot_pfx, const int* row_slot,
+                                         const int* row_kvlen, void* out, int ldo, int R, int H, int t_max,
+                                         int n_slots, float scale, hipStream_t stream) {
+    if (R <= 0 || H <= 0 || t_max <= 0 || cap <= 0 || !pk || !pv || !slot_pfx) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_wave_pfx_kernel<4>), dim3((H + 3) / 4, R), dim3(256), 0, stream,
+                       reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const bf16_t*>(kc),
+                       reinterpret_cast<const bf16_t*>(vc), reinterpret_cast<const bf16_t*>(pk),
+                       reinterpret_cast<const bf16_t*>(pv), cap, slot_pfx, row_slot, row_kvlen,
+                       reinterpret_cast<bf16_t*>(out), ldo, H, t_max, n_slots, scale * 1.4426950408889634f);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_attention_persist_pfx(const void* q, int ldq, const void* kc, const void* vc,
+                                                 const void* pk, const void* pv, int cap, const int* slot_pfx,
+                                                 const int* row_slot, const int* row_kvlen, void* out, int ldo,
+                                                 int R, int H, int t_max, int n_slots, float scale, int blocks,
+                                                 hipStream_t stream) {
+    if (R <= 0 || H <= 0 || t_max <= 0 || blocks <= 0 || cap <= 0 || !pk || !pv || !slot_pfx)
+        return hipErrorInvalidValue;
+    const int need = (R * H + 3) / 4;
+    hipLaunchKernelGGL((attn_persist_pfx_kernel<8>), dim3(blocks < need ? blocks : need), dim3(256), 0, stream,
+                       reinterpret_cast<const bf16_t*>(q), ldq, reinterpret_cast<const bf16_t*>(kc),
+                       reinterpret_cast<const bf16_t*>(vc), reinterpret_cast<const bf16_t*>(pk),
+                       reinterpret_cast<const bf16_t*>(pv), cap, slot_pfx, row_slot, row_kvlen,
+                       reinterpret_cast<bf16_t*>(out), ldo, R, H, t_max, n_slots, scale * 1.4426950408889634f);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t dlms_attention_persist(const void* q, int ldq, const void* kc, const void* vc,
                                              const int* row_slot, const int* row_kvlen, void* out, int ldo, int R,
                                              int H, int t_max, int n_slots, float scale, int blocks,

@@ -265,4 +265,48 @@ extern "C" hipError_t dlms_seen_set(const int* tokens, const int* rows, int R, u
     return hipGetLastError();
 }
 
+// Prompt-prefix cache: broadcast the first pfx[i] key rows of the prefix store into KV-cache slot
+// slots[i], for every layer, K and V, and head.  Cache [L][2][slots][H][t_max][row], store
+// [L][2][H][cap][row] with row = 128 B (bf16) or 64 B (e4m3): per (slot, layer, k/v, head) one
+// contiguous run of pfx * row bytes on both sides, moved as 16-byte chunks with plain stores.
+// One workgroup per (layer * 2 + k/v, listed slot) loops over the heads' chunks.  slots / pfx are
+// read on the device (the staged arrays of a captured prefill); pfx = 0 copies nothing.
+__global__ __launch_bounds__(256) void kv_prefix_fill_kernel(unsigned char* __restrict__ kv,
+                                                             const unsigned char* __restrict__ store,
+                                                             const int* __restrict__ slots,
+                                                             const int* __restrict__ pfx, int n_slots, int H,
+                                                             int t_max, int cap, int row_bytes) {
+    const int lk = blockIdx.x;
+    const int i = blockIdx.y;
+    const int lim = cap < t_max ? cap : t_max;
+    int p = (int)dlms_idx(pfx[i], lim + 1, CHK_PFX_LEN);
+    p = p < 0 ? 0 : (p > lim ? lim : p);  // never past the store's or the slot's rows
+    const int s = slots[i];
+    if (s < 0 || s >= n_slots) {  // the host validates slots; never write outside the cache
+        dlms_idx(s, n_slots, CHK_PFX_SLOT);
+        return;
+    }
+    const int per_head = p * (row_bytes >> 4);  // 16-byte chunks of one head's run
+    const int total = H * per_head;
+    const unsigned char* src = store + (size_t)lk * H * cap * row_bytes;
+    unsigned char* dst = kv + ((size_t)lk * n_slots + s) * H * t_max * row_bytes;
+    for (int c = threadIdx.x; c < total; c += 256) {
+        const int h = c / per_head, rem = c - h * per_head;
+        const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)h * cap * row_bytes + (size_t)rem * 16);
+        *reinterpret_cast<uint4*>(dst + (size_t)h * t_max * row_bytes + (size_t)rem * 16) = v;
+    }
+}
+
+extern "C" hipError_t dlms_kv_prefix_fill(void* kv, const void* store, const int* slots, const int* pfx, int n,
+                                          int layers2, int n_slots, int H, int t_max, int cap, int row_bytes,
+                                          hipStream_t stream) {
+    if (n <= 0 || layers2 <= 0 || n_slots <= 0 || H <= 0 || t_max <= 0 || cap <= 0 || n > 65535 ||
+        (row_bytes != 64 && row_bytes != 128))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kv_prefix_fill_kernel, dim3(layers2, n), dim3(256), 0, stream,
+                       reinterpret_cast<unsigned char*>(kv), reinterpret_cast<const unsigned char*>(store), slots, pfx,
+                       n_slots, H, t_max, cap, row_bytes);
+    return hipGetLastError();
+}
+
 DLMS_CHECK_EXPORT(decode)

@@ -55,6 +55,39 @@ def build_prompt(query: str) -> str:
     return PROMPT_TEMPLATE.format(query=query)
 
 
+# --prefix-cache on: queries whose wrapped prompts are encoded to find the tokens every prompt starts
+# with (different first characters, a digit, a lower-case word: the template's last shared token must
+# not depend on how the query begins)
+PREFIX_PROBES = ("What is a binary search tree?", "explain how Raft elects a leader", "2 + 2 = ?",
+                 "Why is the sky blue?", "describe photosynthesis", "Is P equal to NP?")
+PREFIX_CAPACITY = 64  # rows of the engine's prefix store (the template shares 16 tokens)
+
+
+def prefix_candidate(tok, probes=PREFIX_PROBES) -> list[int]:
+    """The longest common token prefix of ``build_prompt(q)`` over the probe queries: the prompt
+    prefix a server sets on its engine.  The engine still matches per request, so a query whose
+    tokenisation diverges earlier only loses the saving."""
+    enc = [tok.encode(build_prompt(q)) for q in probes]
+    n = 0
+    while all(len(e) > n for e in enc) and len({e[n] for e in enc}) == 1:
+        n += 1
+    return enc[0][:n]
+
+
+def enable_prefix_cache(engine, tok, max_len: int | None = None) -> list[int]:
+    """Set the template's shared tokens as ``engine``'s prompt prefix (at most ``max_len`` of them,
+    default what the engine takes) and return them; ``ValueError`` for an engine without a prefix
+    store or a tokenizer that shares no leading token."""
+    if not getattr(engine, "prefix_capacity", 0) or not hasattr(engine, "set_prompt_prefix"):
+        raise ValueError("--prefix-cache on needs the GPU engine built with a prefix store (one GPU, bf16 weights)")
+    cap = min(engine.prefix_capacity, engine.max_length - 2)
+    prefix = prefix_candidate(tok)[: cap if max_len is None else min(cap, max_len)]
+    if not prefix:
+        raise ValueError("--prefix-cache on: the probe prompts share no leading token")
+    engine.set_prompt_prefix(prefix)
+    return prefix
+
+
 @dataclass
 class _Req:
     ids: list[int]
@@ -158,12 +191,21 @@ class TutoringServicer:
 
 
 def make_engine(model: str, device: str, max_batch: int, max_length: int, weights: str | None = None, seed: int = 0,
-                tp_group=None, weight_dtype: str = "bf16", kv_dtype: str = "bf16", latency_path: bool | None = None):
+                tp_group=None, weight_dtype: str = "bf16", kv_dtype: str = "bf16", latency_path: bool | None = None,
+                prefix_capacity: int = 0):
     """GPU: the HIP engine (TP over ``tp_group`` when given).  CPU: the torch reference engine, or
     the sharded torch slot engine when a (gloo) TP group is given.  ``kv_dtype="fp8"``: the e4m3 KV
     cache (HIP engine) or its reference model (torch engine); not with a TP group.  ``latency_path``
     goes to the HIP engine as it is (None: its default; True also turns the low-batch paths on over
-    an fp8 cache); the torch engines have no such paths and ignore it."""
+    an fp8 cache); the torch engines have no such paths and ignore it.  ``prefix_capacity > 0``: the
+    HIP engine's prompt-prefix store (``set_prompt_prefix``); the torch engines have none
+    (``ValueError``), nor has a TP group."""
+    if prefix_capacity:
+        from ..engine.gpt2_engine import prefix_unsupported
+
+        why = prefix_unsupported(2 if tp_group is not None else 1, weight_dtype == "fp8")
+        if why:
+            raise ValueError(why)
     if kv_dtype == "fp8" and tp_group is not None:
         from ..engine.gpt2_engine import kv_fp8_unsupported
 
@@ -176,7 +218,10 @@ def make_engine(model: str, device: str, max_batch: int, max_length: int, weight
         from ..engine.gpt2_engine import HipGPT2Engine
 
         return HipGPT2Engine(cfg, w, device=device, max_batch=max_batch, max_length=max_length, tp_group=tp_group,
-                             weight_dtype=weight_dtype, kv_dtype=kv_dtype, latency_path=latency_path)
+                             weight_dtype=weight_dtype, kv_dtype=kv_dtype, latency_path=latency_path,
+                             prefix_capacity=prefix_capacity)
+    if prefix_capacity:
+        raise ValueError("the prompt-prefix cache needs the GPU engine (device cuda)")
     if tp_group is not None:
         from ..parallel.tp import TorchSlotEngine
 
@@ -252,6 +297,12 @@ class TutoringServer:
             out.update(hbm_used_gb=round((total - free) / 2**30, 2), hbm_total_gb=round(total / 2**30, 2),
                        kv_cache_gb=round(eng.kv_cache_bytes() / 2**30, 3), slots=eng.max_batch)
             METRICS.set("tutor_hbm_used_gb", out["hbm_used_gb"])
+        if getattr(eng, "prompt_prefix", None):  # --prefix-cache on: how many admissions shared the prefix
+            n = eng.prefix_prompts
+            out.update(prefix_tokens=len(eng.prompt_prefix), prefix_hits=eng.prefix_hits,
+                       prefix_rows_skipped=eng.prefix_rows_skipped, prefix_decode_launches=eng.prefix_decode_launches,
+                       prefix_hit_rate=round(eng.prefix_hits / n, 4) if n else None)
+            METRICS.set("tutor_prefix_hit_rate", eng.prefix_hits / n if n else 0.0)
         if self.batching == "continuous":
             out.update(active=b.active, completed=b.completed, ok=b._error is None and b._thread.is_alive())
         else:
@@ -453,6 +504,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the KV cache holds e4m3 bytes without scales -- half the bytes the decode attention "
                          "streams, twice the slots in the same HBM, reduced precision; one GPU per replica, bf16 weights")
+    ap.add_argument("--prefix-cache", choices=("off", "on"), default="off",
+                    help="on: compute the K/V of the prompt template's shared leading tokens once and keep them in "
+                         "the engine's prefix store -- a query prefills only the rest of its prompt; the tokens "
+                         "served are unchanged; one GPU per replica, bf16 weights")
     ap.add_argument("--latency-path", choices=("auto", "on", "off"), default="auto",
                     help="the GPU engine's low-batch decode paths (latency / mid-batch steps): auto = the engine's "
                          "default (on with the bf16 KV cache, off with --kv-dtype fp8), on / off force them -- on "
@@ -509,6 +564,12 @@ def main(argv=None):
         why = kv_fp8_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
         if why:
             ap.error(f"--kv-dtype fp8: {why}")
+    if args.prefix_cache == "on":
+        from ..engine.gpt2_engine import prefix_unsupported
+
+        why = prefix_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+        if why:
+            ap.error(f"--prefix-cache on: {why}")
     mode = {} if sampling is None else {"sampling": sampling}
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -560,14 +621,18 @@ def main(argv=None):
     else:
         eng = make_engine(args.model, args.device, args.max_batch, args.max_length, args.weights,
                           weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype,
-                          latency_path={"auto": None, "on": True, "off": False}[args.latency_path])
+                          latency_path={"auto": None, "on": True, "off": False}[args.latency_path],
+                          prefix_capacity=PREFIX_CAPACITY if args.prefix_cache == "on" else 0)
     args.max_batch = getattr(eng, "max_batch", 0) or args.max_batch or 64
+    tok = GPT2BPE(args.vocab, args.merges, eos_token_id=eng.cfg.eos_token_id)
+    if args.prefix_cache == "on":  # (ahead of the graph captures below)
+        prefix = enable_prefix_cache(eng, tok)
+        log.info("prompt-prefix cache on: the first %d tokens of every prompt come from the prefix store", len(prefix))
     if args.warm_batch > 0 and hasattr(eng, "warm_decode_graphs"):
         # (a TP proxy mirrors the call to every rank of its group: the captures' warm-up steps run
         # the group's collectives, engine/tp_serving.py)
         n, secs = eng.warm_decode_graphs(args.repetition_penalty, args.warm_batch, **mode)
         log.info("captured %d decode graphs (batch buckets <= %d) in %.1f s", n, args.warm_batch, secs)
-    tok = GPT2BPE(args.vocab, args.merges, eos_token_id=eng.cfg.eos_token_id)
     if pool is not None and hasattr(eng, "admit"):
         srv = PooledTutoringServer(eng, pool, args.max_length, args.repetition_penalty, chunk=args.chunk,
                                    max_queue=args.max_queue, **mode)
@@ -600,6 +665,10 @@ def main(argv=None):
     signal.signal(signal.SIGINT, lambda *a: done.set())
     done.wait()
     srv.stop()
+    if getattr(eng, "prompt_prefix", None) and eng.prefix_prompts:
+        log.info("prompt-prefix cache: %d of %d admitted prompts shared the prefix (%.1f %%), %d prefill rows skipped",
+                 eng.prefix_hits, eng.prefix_prompts, 100.0 * eng.prefix_hits / eng.prefix_prompts,
+                 eng.prefix_rows_skipped)
     if proxy is not None:
         proxy.close()  # releases the followers, which close their engines (below, same order)
         eng = proxy.engine
