@@ -219,6 +219,10 @@ def _bind(L):
     # in-situ tuning knobs (tests and production leave them unset)
     if os.environ.get("DLMS_GEMM_TILE"):
         L.dlms_gemm_force_tile(int(os.environ["DLMS_GEMM_TILE"]))
+    L.dlms_wt_stores_get.argtypes = []
+    L.dlms_wt_stores_get.restype = ctypes.c_int
+    L.dlms_wt_stores_set.argtypes = [ctypes.c_int]
+    L.dlms_wt_stores_set.restype = None
     L.dlms_error_string.argtypes = [ctypes.c_int]
     L.dlms_error_string.restype = ctypes.c_char_p
     L.dlms_gemm_epi_size.restype = ctypes.c_int
@@ -281,6 +285,20 @@ def gemm_tile_count(bm: int, bn: int) -> int:
 
 def gemm_tile_reset():
     lib().dlms_gemm_tile_count(-1, -1)
+
+
+# kernel families whose outputs are stored through L2 (csrc/common.h st_wt*): bits of DLMS_WT_STORES
+WT_GEMM = 1
+
+
+def wt_stores(mask: int | None = None) -> int:
+    """The write-through store mask of the decode-step kernels (``DLMS_WT_STORES``, read once by the
+    library); ``mask``: replace it for the launches that follow (an A/B in one process -- a captured
+    graph keeps the value it was recorded with).  Returns the mask in force before the call."""
+    old = int(lib().dlms_wt_stores_get())
+    if mask is not None:
+        lib().dlms_wt_stores_set(int(mask))
+    return old
 
 
 def _check(err: int, what: str):

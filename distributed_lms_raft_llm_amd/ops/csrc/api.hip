@@ -8,6 +8,11 @@ extern "C" int dlms_abi_version() { return 1; }
 // Size of the GemmEpi struct as compiled, so the Python binding can assert its mirror matches.
 extern "C" int dlms_gemm_epi_size() { return (int)sizeof(GemmEpi); }
 
+// Which decode-step kernel families store their outputs through L2 (common.h st_wt*, DLMS_WT_STORES):
+// a bit mask, bit 0 = the decode GEMM epilogues (WT_GEMM).
+extern "C" int dlms_wt_stores_get() { return dlms_wt_mask(); }
+extern "C" void dlms_wt_stores_set(int mask) { dlms_wt_mask_ref() = mask & WT_ALL; }
+
 // A HIP stream whose kernels may only use ``n_cus`` compute units of the current device, spread
 // evenly (every ``stride``-th CU in the driver's numbering, which interleaves the XCDs): spatial
 // partitioning of the GPU between co-located services -- the relevance gate's encoder passes run on

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
 
@@ -241,6 +242,53 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
     const int xcd = orig % 8;
     const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + orig / 8;
+}
+
+// ------------------------------------------------------------------ write-through output stores
+// The decode GEMMs' outputs are read next by workgroups on other XCDs (or much later: K/V), so keeping
+// the written lines dirty in the writing XCD's L2 buys nothing, and the release at the kernel's end has
+// to write them back.  st_wt{16,8}<true> store through L2 (`sc1`: the line goes to memory as it is
+// written and is dropped from the L2); <false> is the plain store they replace.  The addresses are
+// per-lane 64-bit pointers into buffers that may exceed a buffer descriptor's 4 GB (the KV cache
+// scatter), hence global_store in inline assembly, not a raw buffer store; `s_nop 1` ends each string
+// so that the compiler's next instruction cannot overwrite the data registers before the store has
+// read them.  Vector stores only.  Loads are unchanged: the consumer is always the next kernel, and
+// the kernel boundary stays the only synchronisation.
+// Which kernel families use them is a bit mask, DLMS_WT_STORES, passed to the kernels as an argument,
+// so a family can be A/B-ed in place without a rebuild.  One family has a bit: of the five measured
+// (docs/PERFORMANCE.md round 9) only the GEMM epilogues gained, the others went back to plain stores.
+enum { WT_GEMM = 1, WT_ALL = 1 };
+#define DLMS_WT_DEFAULT WT_GEMM
+// The mask in force: DLMS_WT_STORES (or the default), read once, at the first launch that asks; one
+// instance for the whole library (an inline function's static).  api.hip exports it to the binding:
+// dlms_wt_stores_set() replaces it afterwards (tests run one kernel with the bit off and on in one
+// process); a captured graph keeps the value its launches were recorded with.
+inline int& dlms_wt_mask_ref() {
+    static int mask = [] {
+        const char* e = getenv("DLMS_WT_STORES");
+        return (e != nullptr && e[0] != 0 ? atoi(e) : DLMS_WT_DEFAULT) & WT_ALL;
+    }();
+    return mask;
+}
+inline int dlms_wt_mask() { return dlms_wt_mask_ref(); }
+
+template <bool WT>
+__device__ __forceinline__ void st_wt16(void* p, const uint4 v) {
+    if constexpr (WT) {
+        const u32x4_t d = {v.x, v.y, v.z, v.w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
+    } else {
+        *reinterpret_cast<uint4*>(p) = v;
+    }
+}
+template <bool WT>
+__device__ __forceinline__ void st_wt8(void* p, const uint2 v) {
+    if constexpr (WT) {
+        const unsigned long long d = ((unsigned long long)v.y << 32) | v.x;
+        asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
+    } else {
+        *reinterpret_cast<uint2*>(p) = v;
+    }
 }
 
 // ------------------------------------------------------------------ checked (debug) build

@@ -113,7 +113,8 @@ __device__ __forceinline__ int qkv_chunk_row(int tid, int it, int r0, int M) {
 }
 // KV8: the caches are e4m3 byte caches (64-B key rows); a K/V chunk leaves the staging as 8 bytes
 // (bf16 -> clamp -> packed e4m3, common.h), q is unchanged.
-template <int CHUNKS, int NT, int CPR, bool KV8 = false>
+// WT: the stores go through L2 (common.h st_wt*).
+template <int CHUNKS, int NT, int CPR, bool KV8 = false, bool WT = false>
 __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow, int tid, int r0, int c0, int M,
                                                      const GemmEpi& ep, const int (&sl)[(CHUNKS + NT - 1) / NT],
                                                      const int (&ps)[(CHUNKS + NT - 1) / NT]) {
@@ -136,7 +137,7 @@ __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow,
                 const size_t pos = dlms_idx(ps[it], ep.t_max, CHK_QKV_POS);
                 unsigned char* d8 = reinterpret_cast<unsigned char*>(part == 1 ? ep.k_cache : ep.v_cache) +
                                     ((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim;
-                *reinterpret_cast<uint2*>(d8) = bf16x8_to_e4m3x8(val);
+                st_wt8<WT>(d8, bf16x8_to_e4m3x8(val));
                 continue;
             }
         }
@@ -149,11 +150,11 @@ __device__ __forceinline__ void qkv_staged_store_idx(const char* smem, int srow,
             const size_t pos = dlms_idx(ps[it], ep.t_max, CHK_QKV_POS);
             dst = (part == 1 ? ep.k_cache : ep.v_cache) + ((slot * ep.n_heads + head) * ep.t_max + pos) * 64 + dim;
         }
-        *reinterpret_cast<uint4*>(dst) = val;
+        st_wt16<WT>(dst, val);
     }
 }
 // ... with the indices loaded here, in one batch ahead of the stores (the 256x256 prefill kernel)
-template <int CHUNKS, int NT, int CPR, bool KV8 = false>
+template <int CHUNKS, int NT, int CPR, bool KV8 = false, bool WT = false>
 __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int tid, int r0, int c0, int M,
                                                  const GemmEpi& ep) {
     constexpr int ITER = (CHUNKS + NT - 1) / NT;
@@ -164,7 +165,7 @@ __device__ __forceinline__ void qkv_staged_store(const char* smem, int srow, int
         sl[it] = ep.row_slot[row];
         ps[it] = ep.row_pos[row];
     }
-    qkv_staged_store_idx<CHUNKS, NT, CPR, KV8>(smem, srow, tid, r0, c0, M, ep, sl, ps);
+    qkv_staged_store_idx<CHUNKS, NT, CPR, KV8, WT>(smem, srow, tid, r0, c0, M, ep, sl, ps);
 }
 
 // Launch geometry, computed once on the host (launch_gemm_cfg) so that the kernel's prologue holds no
@@ -205,7 +206,7 @@ __device__ __forceinline__ int xcd_remap_u(unsigned orig, unsigned nwg) {
 template <int BM, int BN, int WM, int WN, int STAGES, int EPI, int IN, int MODE = 0, bool KV8 = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __restrict__ A,
                                                       const void* __restrict__ W, int lda, int ldw,
-                                                      GemmGeo geo, int N, GemmEpi ep) {
+                                                      GemmGeo geo, int N, GemmEpi ep, int wt) {
     constexpr int EB = IN == IN_FP8 ? 1 : 2;    // bytes per element
     constexpr int BKE = GEMM_BK * 2 / EB;       // k-elements per ring step
     constexpr int NW = WM * WN;  // waves per workgroup (4 or 8)
@@ -603,31 +604,45 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_tn_kernel(const void* __res
                 }
         }
         __syncthreads();
-        if constexpr (EPI == EPI_QKV) {
-            if constexpr (EPF) {
-                static_assert(CPR == QCPR, "the prefetched indices follow the staged chunk map");
-                int sl[QITER], ps[QITER];
+        // the write-out; WT (the bf16 decode path, BM <= 64, when the kernel argument `wt` carries
+        // WT_GEMM of DLMS_WT_STORES): through L2 -- the slabs, ff rows, q and K/V are read next on
+        // other XCDs, and the release at the kernel's end then has nothing left to write back
+        // (+1.7 % tokens/s at 1024 queries: profiles/r9_wt_stores_ab.jsonl)
+        auto write_out = [&](auto wt_c) {
+            constexpr bool WT = decltype(wt_c)::value;
+            if constexpr (EPI == EPI_QKV) {
+                if constexpr (EPF) {
+                    static_assert(CPR == QCPR, "the prefetched indices follow the staged chunk map");
+                    int sl[QITER], ps[QITER];
 #pragma unroll
-                for (int it = 0; it < QITER; ++it) sl[it] = (int)sl_pf[it], ps[it] = (int)ps_pf[it];
-                qkv_staged_store_idx<BM * CPR, NT, CPR, KV8>(smem, SROW, tid, m0, n0, M, ep, sl, ps);
+                    for (int it = 0; it < QITER; ++it) sl[it] = (int)sl_pf[it], ps[it] = (int)ps_pf[it];
+                    qkv_staged_store_idx<BM * CPR, NT, CPR, KV8, WT>(smem, SROW, tid, m0, n0, M, ep, sl, ps);
+                } else {
+                    qkv_staged_store<BM * CPR, NT, CPR, KV8, WT>(smem, SROW, tid, m0, n0, M, ep);
+                }
             } else {
-                qkv_staged_store<BM * CPR, NT, CPR, KV8>(smem, SROW, tid, m0, n0, M, ep);
+                for (int c = tid; c < BM * CPR; c += NT) {
+                    const int lr = c / CPR, ch = c - lr * CPR;
+                    const int row = m0 + lr;
+                    if (row >= M) continue;
+                    const uint4 val = *reinterpret_cast<const uint4*>(smem + lr * SROW + ch * 16);
+                    const int col = n0 + ch * (16 / OB);
+                    if constexpr (EPI == EPI_PARTIAL) {
+                        st_wt16<WT>(reinterpret_cast<float*>(ep.out) + (size_t)split * ep.split_stride +
+                                        (size_t)row * ep.ldo + col, val);
+                    } else {
+                        st_wt16<WT>(reinterpret_cast<bf16_t*>(ep.out) + (size_t)row * ep.ldo + col, val);
+                    }
+                }
             }
-            return;
-        }
-        for (int c = tid; c < BM * CPR; c += NT) {
-            const int lr = c / CPR, ch = c - lr * CPR;
-            const int row = m0 + lr;
-            if (row >= M) continue;
-            const uint4 val = *reinterpret_cast<const uint4*>(smem + lr * SROW + ch * 16);
-            const int col = n0 + ch * (16 / OB);
-            if constexpr (EPI == EPI_PARTIAL) {
-                *reinterpret_cast<uint4*>(reinterpret_cast<float*>(ep.out) + (size_t)split * ep.split_stride +
-                                          (size_t)row * ep.ldo + col) = val;
-            } else {
-                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(ep.out) + (size_t)row * ep.ldo + col) = val;
+        };
+        if constexpr (EPF) {
+            if (wt) {
+                write_out(std::true_type{});
+                return;
             }
         }
+        write_out(std::false_type{});
         return;
     }
 
@@ -975,7 +990,7 @@ static hipError_t launch_gemm_cfg(const void* A, int lda, const void* W, int ldw
                                   (int)lds); e != hipSuccess)
         return e;
     hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, STAGES, EPI, IN, MODE, KV8>), dim3(tiles), dim3(64 * WM * WN), lds, stream, A,
-                       W, lda, ldw, geo, N, ep);
+                       W, lda, ldw, geo, N, ep, dlms_wt_mask() & WT_GEMM);
     return hipGetLastError();
 }
 
