@@ -571,7 +571,9 @@ struct AddlnArgs {
 template <int EPI, int NSPLIT, int NV4, int RPW, bool XFIX>
 static hipError_t launch_addln(const AddlnArgs& a, const GemmEpi& ep, hipStream_t stream) {
     constexpr int KBW = NV4 <= 2 ? 4 : (NV4 <= 4 ? 8 : (NV4 == 5 ? 12 : 16));  // >= K/32/4 for K <= 256 * NV4
-    const size_t lds = (size_t)16 * (a.K * 2 + 16);
+    // the LN image, or the 4 waves' K-slice partials that reuse it (larger below K = 128)
+    const size_t img = (size_t)16 * (a.K * 2 + 16), red = (size_t)4 * 64 * 16;
+    const size_t lds = img > red ? img : red;
     hipLaunchKernelGGL((skinny_addln_kernel<EPI, NSPLIT, NV4, RPW, KBW, XFIX>), dim3(a.N / 16), dim3(256), lds, stream,
                        a.x_in, a.x_out, a.ldx, a.parts, a.ldp, a.sstride, a.rbias, a.g, a.b, a.eps, a.W, a.M, a.N, a.K,
                        ep, a.zero_buf, a.zero_chunks, a.xcs);
