@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..models.config import GPT2Config, SamplingParams
+from ..models.config import GenerationControls, GPT2Config, SamplingParams
 from ..utils.metrics import METRICS
 from .weights import GPT2DeviceWeights, prepare_gpt2_weights
 
@@ -171,6 +171,10 @@ def _bucket(n: int) -> int:
     return (n + 255) // 256 * 256
 
 
+# greedy decoding through the sampler (banning GenerationControls): its definition at top_k = 1
+_GREEDY_AS_SAMPLING = SamplingParams(1.0, 1, 1.0, 0)
+
+
 def sampling_unsupported(tp_size: int, fp8: bool) -> str | None:
     """Why an engine of this shape cannot sample (None: it can)."""
     if tp_size > 1:
@@ -201,6 +205,17 @@ def prefix_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
     if fp8_weights:
         return ("the prompt-prefix cache is not supported with fp8 weights: the suffix-only prefill is verified on "
                 "the bf16 GEMMs only; serve prefix_capacity=0 or weight_dtype='bf16'")
+    return None
+
+
+def controls_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
+    """Why an engine of this shape cannot serve ``GenerationControls`` (None: it can)."""
+    if tp_size > 1:
+        return ("generation controls are not supported with tensor parallelism (tp_size > 1): the device bans "
+                "work on one rank's whole vocabulary; serve without controls or TP=1")
+    if fp8_weights:
+        return ("generation controls are not supported with fp8 weights: the fp8 LM head has no f32-logits "
+                "epilogue for the bans; serve without controls or weight_dtype='bf16'")
     return None
 
 
@@ -313,6 +328,8 @@ class HipGPT2Engine:
             why = prefix_unsupported(2 if tp_group is not None else 1, w8)
             if why:
                 raise ValueError(why)
+        if not max_length + 1 < cfg.vocab_size:  # (GenerationControls: a row can never be banned completely)
+            raise ValueError(f"max_length {max_length}: must be below vocab_size - 1 = {cfg.vocab_size - 1}")
         if not torch.cuda.is_available():
             raise RuntimeError("HipGPT2Engine needs a GPU (use TorchGPT2Engine on CPU)")
         ops.lib()  # fail loudly if the kernel library is missing
@@ -558,6 +575,12 @@ class HipGPT2Engine:
         self._logits: torch.Tensor | None = None
         self._rng_seed_host: int | None = None  # the seed in rng_seed (None: never set)
         self._rng_count = 0  # requests admitted since the seed was last set: the next stream id
+        # generation controls (None: none) of the public call in progress (_controls_scope); every
+        # slot's prompt length and the device tables of the stop sequences seen, allocated on the
+        # first call with controls
+        self._controls: GenerationControls | None = None
+        self.prompt_len: torch.Tensor | None = None
+        self._stop_tables: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}
         self._alloc_state()
         self.xgmi = None
         if self.tp_size > 1:
@@ -849,19 +872,32 @@ class HipGPT2Engine:
         hi = lo + B
         seen_rows = self.seen[lo:hi] if seen is None else seen
         P = self.key_parts.shape[1]  # partial keys per row the LM head writes (and the consumer reads)
-        sp = self._sampling
+        sp, ct = self._sampling, self._controls
+        if sp is None and ct is not None and ct.bans:
+            sp = _GREEDY_AS_SAMPLING  # the sampler's definition at top_k = 1: the largest unbanned key
         if sp is not None:
             # sampling: raw f32 logits (the GEMMs' plain f32 epilogues; the penalty moves into the
             # sampler), then one drawn key per row in the first key column
-            self._check_sampling(sp)
+            if self._sampling is not None:
+                self._check_sampling(sp)
             if hidden.dtype == ops.FP8 or self._logits is None:
-                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope")
+                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope / _controls_scope")
             z = self._logits[lo:hi]
             if self.ps_lm and B >= self.PS_LM_MIN_ROWS:
                 ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
             else:
                 ops.gemm(hidden, self.w.lm_head, ops.EPI_F32, out=z)
             P = 1
+            if ct is not None and ct.bans:
+                # controls: -inf at the banned tokens of every live row, between the logits and the sampler
+                if slot_map is None:
+                    ops.logit_bans(z, self.lens[lo:hi], self.finished[lo:hi], self.prompt_len[lo:hi],
+                                   self.out_tokens[lo:hi], ct.no_repeat_ngram_size, ct.min_new_tokens,
+                                   cfg.eos_token_id, cfg.vocab_size)
+                else:
+                    ops.logit_bans(z, self.lens, self.finished, self.prompt_len, self.out_tokens,
+                                   ct.no_repeat_ngram_size, ct.min_new_tokens, cfg.eos_token_id, cfg.vocab_size,
+                                   slot_map=slot_map)
             if slot_map is None:
                 ops.sample_topk_topp(z, seen_rows, self.lens[lo:hi], self.rng_stream[lo:hi], self.rng_seed, penalty,
                                      sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi])
@@ -886,7 +922,22 @@ class HipGPT2Engine:
             keys = self.key_parts[lo:hi, :P]
         else:
             keys = self._gather_keys(B, P)
-        if slot_map is None:
+        if ct is not None and ct.stop:
+            # controls with stop sequences: the same update, which also finishes a row at a match
+            sl, stk = self._stop_tables[ct.stop]
+            l0 = self.w.layers[0]
+            if slot_map is None:
+                ops.decode_update_stop(keys, self.lens[lo:hi], self.finished[lo:hi], self.out_tokens[lo:hi],
+                                       self.seen[lo:hi], self.cur_tok[lo:hi], self.cur_pos[lo:hi],
+                                       self.cur_kvlen[lo:hi], self.w.wte, self.w.wpe, self.x[lo:hi], cfg.eos_token_id,
+                                       self.max_length, self.prompt_len[lo:hi], sl, stk,
+                                       ln=(l0.ln1_g, l0.ln1_b, cfg.layer_norm_epsilon) if ln1_out is not None else None,
+                                       h=ln1_out)
+            else:
+                ops.decode_update_stop(keys, self.lens, self.finished, self.out_tokens, self.seen, self.cur_tok,
+                                       self.cur_pos, self.cur_kvlen, self.w.wte, self.w.wpe, self.x, cfg.eos_token_id,
+                                       self.max_length, self.prompt_len, sl, stk, slot_map=slot_map)
+        elif slot_map is None:
             l0 = self.w.layers[0]
             ops.decode_update(keys, self.lens[lo:hi], self.finished[lo:hi], self.out_tokens[lo:hi],
                               self.seen[lo:hi], self.cur_tok[lo:hi], self.cur_pos[lo:hi], self.cur_kvlen[lo:hi],
@@ -913,6 +964,34 @@ class HipGPT2Engine:
             yield
         finally:
             self._sampling = prev
+
+    @contextlib.contextmanager
+    def _controls_scope(self, controls: "GenerationControls | None"):
+        """The generation controls of one public call, like ``_sampling_scope``: every LM head and
+        update issued (or captured) inside applies them; graphs are keyed by them.  None: none,
+        exactly the calls made before."""
+        if controls is not None:
+            self._check_controls(controls)
+            # (outside any capture: graph pools must not own these)
+            if self.prompt_len is None:
+                self.prompt_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            if controls.bans and self._logits is None:
+                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
+                                           device=self.device)
+            if controls.stop and controls.stop not in self._stop_tables:
+                self._stop_tables[controls.stop] = ops.stop_table(controls.stop, self.device)
+        prev, self._controls = self._controls, controls
+        try:
+            yield
+        finally:
+            self._controls = prev
+
+    def _check_controls(self, controls):
+        if not isinstance(controls, GenerationControls):
+            raise TypeError("controls: a GenerationControls (models/config.py) or None")
+        why = controls_unsupported(self.tp_size, self.w.fp8)
+        if why:
+            raise ValueError(why)
 
     def _check_sampling(self, sampling):
         if not isinstance(sampling, SamplingParams):
@@ -941,9 +1020,11 @@ class HipGPT2Engine:
         return list(range(first, first + n))
 
     def _skey(self) -> tuple:
-        """What the captured graphs depend on beyond their shapes: the sampling mode, and whether the
-        decode attention reads the prefix store."""
+        """What the captured graphs depend on beyond their shapes: the sampling mode, the generation
+        controls, and whether the decode attention reads the prefix store."""
         key = () if self._sampling is None else self._sampling.shape_key
+        if self._controls is not None:
+            key = key + self._controls.shape_key
         return key + ("pfx",) if self._pfx_decode() else key
 
     def _overlap_ok(self, B: int) -> bool:
@@ -1014,8 +1095,9 @@ class HipGPT2Engine:
         from ..ops.dataflow import MAX_ROWS
 
         # (the launch-per-op path serves row counts whose stream window outgrows the LDS ring)
-        # (sampling: the dataflow kernel's LM head is greedy; launch-per-op serves those rows)
-        return (self.dataflow and self._sampling is None and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
+        # (sampling: the dataflow kernel's LM head is greedy; launch-per-op serves those rows.
+        # Generation controls: its commit block knows none of them; the same)
+        return (self.dataflow and self._sampling is None and self._controls is None and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
                 and time.monotonic() >= self._df_off_until and self._df_decoder().fits(B))
 
     def _df_run(self, B: int, steps: int, penalty: float) -> bool:
@@ -1431,6 +1513,8 @@ class HipGPT2Engine:
             self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
         ops.seen_set(self.seen, slot_d, tokens_d)
         self.lens.index_copy_(0, idx, lens_d)
+        if self._controls is not None:  # the prompts' lengths: what min_new_tokens and the stops count from
+            self.prompt_len.index_copy_(0, idx, lens_d)
         self.finished.index_copy_(0, idx, fin_d)
         # the LM head of the first token reads the prompts' bitmaps as rows [0, n)
         seen_d = self.seen.index_select(0, idx)
@@ -1574,19 +1658,28 @@ class HipGPT2Engine:
     # ------------------------------------------------------------------ slot API (continuous batching)
     @torch.no_grad()
     def admit(self, prompts: list[list[int]], slots: list[int], repetition_penalty: float = 1.2,
-              sampling: SamplingParams | None = None):
+              sampling: SamplingParams | None = None, controls: GenerationControls | None = None):
         """Prefill new sequences into free ``slots`` of the running batch (first token included).
         ``sampling``: draw their tokens instead; each takes the next stream id (the count of requests
         admitted since the seed was last set: ``reseed``, or a ``sampling.seed`` other than the
-        current one)."""
+        current one).  ``controls``: the slots' generation controls; every later call that serves
+        these slots passes the same."""
+        if controls is not None:
+            with self._controls_scope(controls):
+                return self.admit(prompts, slots, repetition_penalty, sampling)
         with self._sampling_scope(sampling):
             self._prefill_into([list(p) for p in prompts], list(slots), repetition_penalty,
                                self._next_streams(len(prompts), sampling))
 
     @torch.no_grad()
-    def decode(self, B: int, steps: int, repetition_penalty: float = 1.2, sampling: SamplingParams | None = None):
+    def decode(self, B: int, steps: int, repetition_penalty: float = 1.2, sampling: SamplingParams | None = None,
+               controls: GenerationControls | None = None):
         """``steps`` decode steps over slots [0, B) (finished/inert slots are no-ops): greedy, or
-        sampled with ``sampling`` under the slots' stream ids (``admit``)."""
+        sampled with ``sampling`` under the slots' stream ids (``admit``); under ``controls``, the
+        ones the slots were admitted with."""
+        if controls is not None:
+            with self._controls_scope(controls):
+                return self.decode(B, steps, repetition_penalty, sampling)
         with self._sampling_scope(sampling):
             self._decode(B, steps, repetition_penalty)
 
@@ -1612,11 +1705,15 @@ class HipGPT2Engine:
 
     @torch.no_grad()
     def warm_decode_graphs(self, repetition_penalty: float = 1.2, max_batch: int | None = None,
-                           sampling: SamplingParams | None = None) -> tuple[int, float]:
+                           sampling: SamplingParams | None = None,
+                           controls: GenerationControls | None = None) -> tuple[int, float]:
         """Capture the decode-step graphs ``decode()`` would capture on first use (one step and one
         replay's worth of steps per batch bucket up to ``max_batch``; the dataflow buckets need none)
         so a server's first burst of queries does not pay the captures.  ``sampling``: the graphs of
-        that sampling mode.  Returns (graphs, seconds)."""
+        that sampling mode; ``controls``: of those generation controls.  Returns (graphs, seconds)."""
+        if controls is not None:
+            with self._controls_scope(controls):
+                return self.warm_decode_graphs(repetition_penalty, max_batch, sampling)
         with self._sampling_scope(sampling):
             return self._warm_decode_graphs(repetition_penalty, max_batch)
 
@@ -1720,10 +1817,15 @@ class HipGPT2Engine:
     # ------------------------------------------------------------------ public API
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
-                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None) -> list[list[int]]:
+                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
+                 controls: GenerationControls | None = None) -> list[list[int]]:
         """Full sequences (prompt echoed) of ``prompts``: greedy, or with ``sampling`` drawn under
         ``sampling.seed`` with prompt i on stream i -- set anew on every call, so equal calls return
-        equal outputs."""
+        equal outputs.  ``controls`` (a ``GenerationControls``): n-gram blocking, a minimum length and
+        stop sequences, applied on the device inside the decode loop."""
+        if controls is not None:
+            with self._controls_scope(controls):
+                return self.generate(prompts, max_length, repetition_penalty, stats, sampling)
         if sampling is None:
             return self._generate(prompts, max_length, repetition_penalty, stats, None)
         with self._sampling_scope(sampling):
@@ -1860,9 +1962,11 @@ class TorchGPT2Engine:
 
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
-                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None) -> list[list[int]]:
+                 stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
+                 controls: GenerationControls | None = None) -> list[list[int]]:
         """``sampling``: tokens drawn by ``models.gpt2.reference_sample`` under ``sampling.seed``,
-        prompt i on stream i (the HIP engine's rule)."""
+        prompt i on stream i (the HIP engine's rule).  ``controls``: the bans and stops of
+        ``models.gpt2.banned_tokens`` / ``stop_hit``."""
         from ..models.gpt2 import reference_generate
 
         T = self.max_length if max_length is None else max_length
@@ -1871,7 +1975,7 @@ class TorchGPT2Engine:
         t0 = time.perf_counter()
         if prompts:
             gen = reference_generate(self.model, prompts, max_length=T, repetition_penalty=repetition_penalty,
-                                     sampling=sampling, streams=list(run_idx))
+                                     sampling=sampling, streams=list(run_idx), controls=controls)
             for i, o in zip(run_idx, gen):
                 out[i] = o
         out_run = [out[i] for i in run_idx]

@@ -20,7 +20,8 @@ Engine protocol (``HipGPT2Engine`` implements it; tests use a CPU fake):
     max_batch, max_length, cfg.eos_token_id
     admit(prompts, slots, repetition_penalty)   prefill + first token into those slots
     decode(B, steps, repetition_penalty)        ``steps`` decode steps over slots [0, B)
-                                                (both with ``sampling=`` when the batcher samples)
+                                                (both with ``sampling=`` when the batcher samples and
+                                                ``controls=`` when it has generation controls)
     finished_flags(B) -> list[int]              per-slot stop flags
     collect(slots) -> list[list[int]]           prompt + generated tokens
     flags_async(B), collect_async(slots)        optional: the same as handles with .result()
@@ -91,15 +92,21 @@ class Overloaded(RuntimeError):
 
 class ContinuousBatcher:
     def __init__(self, engine, repetition_penalty: float = 1.2, chunk: int = 8, max_admit: int | None = None,
-                 name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0, sampling=None):
+                 name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0, sampling=None,
+                 controls=None):
         """``max_queue``: queries allowed to wait for a free KV slot before ``submit`` raises
         ``Overloaded`` (0 = unbounded; the tutoring servers default to one batch of slots).
         ``sampling`` (a ``SamplingParams``): tokens are drawn instead of greedy; it is forwarded to
         the engine's ``admit`` / ``decode`` as ``sampling=`` -- only when set, so greedy engines are
-        called exactly as before."""
+        called exactly as before.  ``controls`` (a ``GenerationControls``): n-gram blocking, a minimum
+        length and stop sequences, forwarded the same way as ``controls=`` (results keep their stop
+        tokens, as they keep EOS)."""
         self.engine = engine
         self.sampling = sampling
+        self.controls = controls
         self._mode = {} if sampling is None else {"sampling": sampling}
+        if controls is not None:
+            self._mode["controls"] = controls
         self.max_queue = int(max_queue or 0)
         self.rejected = 0
         env_prio = os.environ.get("DLMS_BATCHER_STREAM_PRIORITY")

@@ -133,6 +133,59 @@ class SamplingParams:
         return (float(self.temperature), int(self.top_k), float(self.top_p))
 
 
+CONTROLS_MAX_STOP = 4       # stop sequences per GenerationControls (ops/csrc/decode.hip STOP_MAX_SEQS)
+CONTROLS_MAX_STOP_LEN = 8   # tokens per stop sequence (STOP_MAX_LEN)
+
+
+@dataclass(frozen=True)
+class GenerationControls:
+    """Opt-in generation controls beside the repetition penalty, with HF's semantics
+    (``NoRepeatNGramLogitsProcessor``, ``MinNewTokensLengthLogitsProcessor``, stop sequences on
+    token ids); the definition is in ``ops/csrc/controls.hip`` and, in Python,
+    ``models.gpt2.banned_tokens`` / ``stop_hit``.
+
+    ``no_repeat_ngram_size`` n (0: off): no n-gram occurs twice in a sequence (prompt included).
+    ``min_new_tokens``: EOS is banned until that many tokens have been generated.
+    ``stop``: up to ``CONTROLS_MAX_STOP`` token sequences of 1 .. ``CONTROLS_MAX_STOP_LEN`` ids; a row
+    finishes once its generated tokens end with one of them (the stop tokens stay in the output)."""
+
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+    stop: tuple = ()
+
+    def __post_init__(self):
+        n, m, stop = self.no_repeat_ngram_size, self.min_new_tokens, self.stop
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError(f"no_repeat_ngram_size {n!r}: an integer >= 0 (0: off)")
+        if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+            raise ValueError(f"min_new_tokens {m!r}: an integer >= 0")
+        if isinstance(stop, (str, bytes)) or not isinstance(stop, (tuple, list)):
+            raise ValueError(f"stop {stop!r}: a tuple of token-id tuples")
+        if len(stop) > CONTROLS_MAX_STOP:
+            raise ValueError(f"stop: at most {CONTROLS_MAX_STOP} sequences, got {len(stop)}")
+        norm = []
+        for s in stop:
+            if isinstance(s, (str, bytes)) or not isinstance(s, (tuple, list)):
+                raise ValueError(f"stop sequence {s!r}: a tuple of token ids")
+            if not 1 <= len(s) <= CONTROLS_MAX_STOP_LEN:
+                raise ValueError(f"stop sequence {s!r}: 1 .. {CONTROLS_MAX_STOP_LEN} token ids")
+            for t in s:
+                if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 31:
+                    raise ValueError(f"stop sequence {s!r}: token ids are integers in [0, 2^31)")
+            norm.append(tuple(s))
+        object.__setattr__(self, "stop", tuple(norm))
+
+    @property
+    def bans(self) -> bool:
+        """Whether tokens are banned (the LM head then writes f32 logits for ``logit_bans``)."""
+        return self.no_repeat_ngram_size > 0 or self.min_new_tokens > 0
+
+    @property
+    def shape_key(self) -> tuple:
+        """What a captured graph bakes in: all of it."""
+        return ("ctl", self.no_repeat_ngram_size, self.min_new_tokens, self.stop)
+
+
 @dataclass
 class GenerationConfig:
     """Decode semantics of the reference ``model.generate`` call (tutoring_server.py:21-29).
@@ -140,6 +193,8 @@ class GenerationConfig:
     ``do_sample`` is unset there, so decoding is greedy by default.  With ``do_sample`` set,
     ``sampling()`` gives the ``SamplingParams`` (``temperature``/``top_k``/``top_p`` and
     ``seed``) that the engines, the scheduler and the tutor server take as ``sampling=``.
+    ``controls()`` gives the ``GenerationControls`` (``no_repeat_ngram_size``, ``min_new_tokens``,
+    ``stop``) they take as ``controls=``, or None when all three are off.
     """
 
     max_length: int = 150  # total length, prompt included
@@ -156,3 +211,12 @@ class GenerationConfig:
         if not self.do_sample:
             return None
         return SamplingParams(self.temperature, self.top_k, self.top_p, self.seed)
+
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+    stop: tuple = ()
+
+    def controls(self) -> "GenerationControls | None":
+        if not (self.no_repeat_ngram_size or self.min_new_tokens or self.stop):
+            return None
+        return GenerationControls(self.no_repeat_ngram_size, self.min_new_tokens, tuple(self.stop))

@@ -181,11 +181,14 @@ def reference_generate(
     eos_token_id: int | None = None,
     sampling=None,
     streams: list[int] | None = None,
+    controls=None,
 ) -> list[list[int]]:
     """Batched greedy + repetition-penalty decode.  Returns full sequences (prompt
     echoed, as ``generate`` does), each stopping at EOS (inclusive) or ``max_length``.
     ``sampling`` (a ``SamplingParams``): every token is drawn by ``reference_sample`` instead, row b
-    with stream id ``streams[b]`` (default b) at position = the index the token is written to."""
+    with stream id ``streams[b]`` (default b) at position = the index the token is written to.
+    ``controls`` (a ``GenerationControls``): the logits of ``banned_tokens`` become -inf ahead of the
+    penalty, and a row also stops once ``stop_hit``."""
     cfg = model.cfg
     eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
     B = len(prompts)
@@ -213,6 +216,12 @@ def reference_generate(
     h_last = hidden[rows, last]
     while True:
         logits = model.logits(h_last)
+        if controls is not None and controls.bans:
+            for b in range(B):
+                if not done[b]:
+                    ban = banned_tokens(seqs[b], len(prompts[b]), controls, eos)
+                    if ban:
+                        logits[b, torch.tensor(ban, device=dev)] = float("-inf")
         if sampling is None:
             nxt = torch.argmax(apply_repetition_penalty(logits, seen, repetition_penalty), dim=-1)
         else:
@@ -228,6 +237,8 @@ def reference_generate(
             seen[b, t] = True
             if t == eos or len(seqs[b]) >= max_length:
                 done[b] = True
+            elif controls is not None and stop_hit(seqs[b], len(prompts[b]), controls.stop):
+                done[b] = True
         if all(done):
             break
         cur_pos = torch.tensor([min(len(s) - 1, max_length - 1) for s in seqs], device=dev)
@@ -235,6 +246,114 @@ def reference_generate(
         hidden = model.forward(cur_tok[:, None], cur_pos[:, None], cache, rows)
         h_last = hidden[:, 0]
     return seqs
+
+
+# ---------------------------------------------------------------------------------------------
+# Generation controls: the normative Python definition (ops/csrc/controls.hip has the same text)
+# ---------------------------------------------------------------------------------------------
+def banned_tokens(seq, prompt_len: int, controls, eos: int) -> list[int]:
+    """The token ids whose logit is -inf for the next token of ``seq`` (prompt of ``prompt_len``
+    tokens included), sorted.  With L = len(seq) and n = ``controls.no_repeat_ngram_size``: if
+    n > 0 and L + 1 >= n, ``seq[i+n-1]`` for every 0 <= i <= L-n with
+    ``seq[i : i+n-1] == seq[L-n+1 : L]`` (n = 1: every token of ``seq``) -- HF's
+    ``NoRepeatNGramLogitsProcessor``; and ``eos`` while ``L - prompt_len < controls.min_new_tokens``
+    -- HF's ``MinNewTokensLengthLogitsProcessor``."""
+    seq = [int(t) for t in seq]
+    L, n = len(seq), int(controls.no_repeat_ngram_size)
+    ban = set()
+    if n > 0 and L + 1 >= n:
+        tail = seq[L - n + 1: L]
+        for i in range(L - n + 1):
+            if seq[i: i + n - 1] == tail:
+                ban.add(seq[i + n - 1])
+    if L - int(prompt_len) < int(controls.min_new_tokens):
+        ban.add(int(eos))
+    return sorted(ban)
+
+
+def stop_hit(seq, prompt_len: int, stop) -> bool:
+    """Whether ``seq``, whose last token was just written at index p = len(seq) - 1, ends with one of
+    the ``stop`` sequences wholly inside its generated part: for some s of length m,
+    ``p + 1 - m >= prompt_len`` and ``seq[p+1-m : p+1] == s``."""
+    L = len(seq)
+    for s in stop:
+        m = len(s)
+        if m and L - m >= prompt_len and [int(t) for t in seq[L - m:]] == [int(t) for t in s]:
+            return True
+    return False
+
+
+def _controls_rows(logits: torch.Tensor, seq: list[int], prompt_len: int, repetition_penalty: float, controls,
+                   eos: int, eps: float) -> dict:
+    """The margin rule on the oracle's ``logits`` rows (row j predicts ``seq[prompt_len + j]``)
+    with the bans of ``controls`` applied at each position."""
+    n = logits.shape[0]
+    dev = logits.device
+    logits = logits.clone()
+    seen = torch.zeros(n, logits.shape[1], dtype=torch.bool, device=dev)
+    banned_got = []
+    for j in range(n):
+        seen[j, torch.tensor(seq[: prompt_len + j], device=dev)] = True
+        if controls is not None and controls.bans:
+            ban = banned_tokens(seq[: prompt_len + j], prompt_len, controls, eos)
+            if ban:
+                logits[j, torch.tensor(ban, device=dev)] = float("-inf")
+            if seq[prompt_len + j] in ban:
+                banned_got.append(prompt_len + j)
+    logits = apply_repetition_penalty(logits, seen, repetition_penalty)
+    top = logits.topk(2, dim=-1)
+    margin = (top.values[:, 0] - top.values[:, 1]).tolist()
+    want = top.indices[:, 0].tolist()
+    out = {"positions": n, "decisive": 0, "mismatches": [], "min_margin": min(margin)}
+    for j in range(n):
+        got = seq[prompt_len + j]
+        if prompt_len + j in banned_got:  # whatever the margin: no sampler may pick a banned token
+            out["mismatches"].append((prompt_len + j, got, want[j], float("inf")))
+        if margin[j] > eps:
+            out["decisive"] += 1
+            if got != want[j] and prompt_len + j not in banned_got:
+                out["mismatches"].append((prompt_len + j, got, want[j], margin[j]))
+    return out
+
+
+@torch.no_grad()
+def teacher_forced_controls_check(model: GPT2Reference, seq: list[int], prompt_len: int,
+                                  repetition_penalty: float = 1.2, controls=None, eps: float = 0.05,
+                                  eos_token_id: int | None = None) -> dict:
+    """``teacher_forced_check`` for a greedy sequence generated under ``controls``: the bans of
+    ``banned_tokens`` are applied to the oracle's logits at each position (-inf ahead of the
+    penalty); a position is decisive when top-1 minus top-2 among the unbanned penalised logits
+    exceeds ``eps``, and there the token must be the oracle's choice.  A banned token in ``seq`` is a
+    mismatch at any margin.  Same result dict."""
+    return teacher_forced_controls_check_batch(model, [seq], [prompt_len], repetition_penalty, controls, eps,
+                                               eos_token_id=eos_token_id)[0]
+
+
+@torch.no_grad()
+def teacher_forced_controls_check_batch(model: GPT2Reference, seqs: list[list[int]], prompt_lens: list[int],
+                                        repetition_penalty: float = 1.2, controls=None, eps: float = 0.05,
+                                        chunk: int = 16, eos_token_id: int | None = None) -> list[dict]:
+    """``teacher_forced_controls_check`` for many sequences (one padded forward per ``chunk`` rows, as
+    ``teacher_forced_check_batch`` runs it)."""
+    cfg, dev = model.cfg, model.device
+    eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+    out: list[dict] = []
+    for c0 in range(0, len(seqs), chunk):
+        rows = seqs[c0: c0 + chunk]
+        pls = prompt_lens[c0: c0 + chunk]
+        Bc = len(rows)
+        S = max(len(s) for s in rows)
+        toks = torch.tensor([s + [s[-1]] * (S - len(s)) for s in rows], device=dev)
+        pos = torch.arange(S, device=dev)[None].expand(Bc, S).contiguous()
+        cache = KVCache.allocate(cfg, Bc, S, dtype=model.dtype, device=dev)
+        hidden = model.forward(toks, pos, cache, torch.arange(Bc, device=dev))
+        for b, (s, pl) in enumerate(zip(rows, pls)):
+            if len(s) <= pl:
+                out.append({"positions": 0, "decisive": 0, "mismatches": [], "min_margin": float("inf")})
+                continue
+            out.append(_controls_rows(model.logits(hidden[b, pl - 1: len(s) - 1]), s, pl, repetition_penalty,
+                                      controls, eos, eps))
+    return out
 
 
 @torch.no_grad()
@@ -480,14 +599,15 @@ def reference_sample(logits_f32, seen, penalty: float, params, stream: int, posi
 
 @torch.no_grad()
 def teacher_forced_sampling_check(model: GPT2Reference, seq: list[int], prompt_len: int, repetition_penalty: float,
-                                  params, eps: float = 0.05) -> dict:
+                                  params, eps: float = 0.05, controls=None, eos_token_id: int | None = None) -> dict:
     """Oracle for a SAMPLED sequence: one fp32 forward over ``seq`` (teacher forcing); a generated
     token is a mismatch when the oracle says no sampler within a logit error of ``eps`` could have
     drawn it -- (a) its penalised oracle logit is more than ``eps`` below the ``top_k``-th largest,
     or (b) the oracle probability mass (softmax at the temperature over the top-k) of the tokens
     whose logit beats it by more than ``eps`` is >= ``top_p * exp(2 eps / T)``: those tokens rank
     above it under any eps-perturbation, and an eps-error scales a softmax ratio by at most
-    exp(2 eps / T), so the nucleus closes before it.
+    exp(2 eps / T), so the nucleus closes before it.  ``controls``: the oracle's logits of
+    ``banned_tokens`` are -inf at each position, so a banned token in ``seq`` is "below top-k".
 
     Returns {"positions", "mismatches": [(i, got, reason, value)]}."""
     cfg = model.cfg
@@ -505,6 +625,12 @@ def teacher_forced_sampling_check(model: GPT2Reference, seq: list[int], prompt_l
     seen = torch.zeros(n, cfg.vocab_size, dtype=torch.bool, device=dev)
     for j in range(n):
         seen[j, torch.tensor(seq[: prompt_len + j], device=dev)] = True
+    if controls is not None and controls.bans:
+        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+        for j in range(n):
+            ban = banned_tokens(seq[: prompt_len + j], prompt_len, controls, eos)
+            if ban:
+                logits[j, torch.tensor(ban, device=dev)] = float("-inf")
     logits = apply_repetition_penalty(logits, seen, repetition_penalty).double()
     k = min(int(params.top_k), cfg.vocab_size)
     T, top_p = float(params.temperature), float(params.top_p)

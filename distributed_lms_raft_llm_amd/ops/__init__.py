@@ -27,14 +27,14 @@ LIB_DIR = _HERE / "_lib"
 LIB_PATH = LIB_DIR / "libdlms_hip.so"
 # debug variant: device-side range checks on every data-dependent index (common.h, DLMS_DEVICE_CHECKS)
 CHECKED_LIB_PATH = LIB_DIR / "libdlms_hip_checked.so"
-CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "sample")
+CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "sample", "controls")
 CHECK_SITES = {1: "embed token id", 2: "position id", 3: "decode_update slot_map", 4: "decode_update token id",
                5: "decode_update sequence length", 6: "seen_set row", 7: "QKV scatter slot", 8: "QKV scatter position",
                9: "attention slot", 10: "BERT token id", 11: "seen_set token id", 12: "sampler slot_map",
                13: "sampled token id", 14: "prefix fill slot", 15: "prefix fill length",
-               16: "attention prefix length"}
+               16: "attention prefix length", 17: "logit_bans slot_map", 18: "logit_bans sequence length"}
 SOURCES = ["api.hip", "gemm.hip", "norm.hip", "attention.hip", "decode.hip", "encoder.hip", "xgmi.hip", "skinny.hip", "gemm_ps.hip",
-           "dataflow.hip", "mid.hip", "sample.hip"]
+           "dataflow.hip", "mid.hip", "sample.hip", "controls.hip"]
 ARCH = os.environ.get("DLMS_OFFLOAD_ARCH", "gfx950")
 
 EPI_BF16, EPI_GELU_TANH, EPI_GELU_ERF, EPI_F32, EPI_QKV, EPI_ARGMAX, EPI_PARTIAL = range(7)
@@ -151,6 +151,8 @@ def _bind(L):
         "dlms_embed": [P, P, P, P, P, I, I, I, I, I, P],
         "dlms_decode_update": [P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, I, P, I, P, P, P, P, P, P, I, I,
                                I, I, I, I, I, P, P, F, P, I, P],
+        "dlms_decode_update_stop": [P, I, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, I, P, I, P, P, P, P, P, P, I,
+                                    I, I, I, I, I, I, P, P, F, P, I, P, P, P, P],
         "dlms_argmax_reduce": [P, I, ctypes.c_longlong, P, I, P],
         "dlms_seen_set": [P, P, I, P, I, I, P],
         "dlms_kv_prefix_fill": [P, P, P, P, I, I, I, I, I, I, I, P],
@@ -182,6 +184,7 @@ def _bind(L):
         "dlms_sample_topk_topp": [P, ctypes.c_longlong, P, I, P, P, P, I, P, F, ctypes.c_double, I, ctypes.c_double, I,
                                   P, ctypes.c_longlong, I, P],
         "dlms_philox4x32_10": [P, P, I, P],
+        "dlms_logit_bans": [P, ctypes.c_longlong, P, P, P, P, ctypes.c_longlong, I, P, I, I, I, I, I, I, P],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -779,7 +782,8 @@ def kv_prefix_fill(kv: torch.Tensor, store: torch.Tensor, slots: torch.Tensor, p
 
 
 def decode_update(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok, cur_pos, cur_kvlen, wte, wpe, x,
-                  eos: int, t_max: int, slot_map: torch.Tensor | None = None, ln=None, h: torch.Tensor | None = None):
+                  eos: int, t_max: int, slot_map: torch.Tensor | None = None, ln=None, h: torch.Tensor | None = None,
+                  _stop=None):
     """keys: int64 [R, P] (row-major partial keys) or a transposed view [P, R].T (gathered per-rank
     keys); the token of row i is the argmax over its P keys and updates sequence slot
     ``slot_map[i]`` (default: slot i).  ``ln=(gamma, beta, eps)`` + ``h``: also write
@@ -818,6 +822,16 @@ def decode_update(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok,
                 raise ValueError(f"decode_update: {n} must be contiguous [D]")
         if h.shape[0] < nslots or h.shape[1] < D or h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 8:
             raise ValueError("decode_update: h must be [>= slots, >= D] bf16 rows, 8-B aligned")
+    if _stop is not None:  # (decode_update_stop: the same update with the stop-sequence check)
+        prompt_len, stop_len, stop_tok = _stop
+        _check(lib().dlms_decode_update_stop(_p(keys), P, keys.stride(0), keys.stride(1), _p(slot_map), _p(lens),
+                                             _p(finished), _p(out_tokens), out_tokens.stride(0), _p(seen),
+                                             seen.stride(0), _p(cur_tok), _p(cur_pos), _p(cur_kvlen), _p(wte), _p(wpe),
+                                             _p(x), x.stride(0), B, D, eos, t_max, lens.numel(), wte.shape[0], _p(g),
+                                             _p(b), float(eps), _p(h), h.stride(0) if h is not None else 0,
+                                             _p(prompt_len), _p(stop_len), _p(stop_tok), _stream()),
+               "dlms_decode_update_stop")
+        return
     _check(lib().dlms_decode_update(_p(keys), P, keys.stride(0), keys.stride(1), _p(slot_map), _p(lens), _p(finished),
                                     _p(out_tokens),
                                     out_tokens.stride(0), _p(seen), seen.stride(0), _p(cur_tok), _p(cur_pos),
@@ -825,6 +839,47 @@ def decode_update(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok,
                                     lens.numel(), wte.shape[0], _p(g), _p(b), float(eps), _p(h),
                                     h.stride(0) if h is not None else 0, _stream()),
            "dlms_decode_update")
+
+
+STOP_MAX_SEQS, STOP_MAX_LEN = 4, 8  # decode.hip; models/config.py CONTROLS_MAX_STOP / CONTROLS_MAX_STOP_LEN
+
+
+def stop_table(stop, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """The device table of ``stop`` (up to STOP_MAX_SEQS token sequences of 1 .. STOP_MAX_LEN ids) that
+    ``decode_update_stop`` reads: (lengths int32 [STOP_MAX_SEQS], tokens int32 [STOP_MAX_SEQS, STOP_MAX_LEN]),
+    unused sequences of length 0."""
+    stop = [list(s) for s in stop]
+    if len(stop) > STOP_MAX_SEQS or any(not 1 <= len(s) <= STOP_MAX_LEN for s in stop):
+        raise ValueError(f"stop_table: at most {STOP_MAX_SEQS} sequences of 1 .. {STOP_MAX_LEN} token ids")
+    if any(not 0 <= int(t) < 2 ** 31 for s in stop for t in s):
+        raise ValueError("stop_table: token ids in [0, 2^31)")
+    ln = torch.zeros(STOP_MAX_SEQS, dtype=torch.int32)
+    tk = torch.zeros(STOP_MAX_SEQS, STOP_MAX_LEN, dtype=torch.int32)
+    for i, s in enumerate(stop):
+        ln[i] = len(s)
+        tk[i, : len(s)] = torch.tensor(s, dtype=torch.int32)
+    return ln.to(device), tk.to(device)
+
+
+def decode_update_stop(keys: torch.Tensor, lens, finished, out_tokens, seen, cur_tok, cur_pos, cur_kvlen, wte, wpe, x,
+                       eos: int, t_max: int, prompt_len: torch.Tensor, stop_len: torch.Tensor, stop_tok: torch.Tensor,
+                       slot_map: torch.Tensor | None = None, ln=None, h: torch.Tensor | None = None):
+    """``decode_update`` that also finishes a row whose generated tokens now end with a stop sequence
+    of the table (``stop_table``): after the token is written at index p, for a sequence s of length m,
+    ``p + 1 - m >= prompt_len[slot]`` and ``seq[p+1-m : p+1] == s``.  Everything else it writes is what
+    ``decode_update`` writes, bit for bit.  The definition: ``controls.hip`` / ``models.gpt2.stop_hit``."""
+    _req(prompt_len, torch.int32, "prompt_len", 1)
+    _req(stop_len, torch.int32, "stop_len", 1)
+    _req(stop_tok, torch.int32, "stop_tok", 2)
+    nslots = keys.shape[0] if slot_map is None else lens.numel()
+    if prompt_len.numel() < nslots:
+        raise ValueError("prompt_len too short")
+    if stop_len.numel() != STOP_MAX_SEQS or tuple(stop_tok.shape) != (STOP_MAX_SEQS, STOP_MAX_LEN) or \
+            not stop_tok.is_contiguous():
+        raise ValueError(f"decode_update_stop: a stop_table ([{STOP_MAX_SEQS}] lengths, "
+                         f"[{STOP_MAX_SEQS}, {STOP_MAX_LEN}] contiguous tokens)")
+    decode_update(keys, lens, finished, out_tokens, seen, cur_tok, cur_pos, cur_kvlen, wte, wpe, x, eos, t_max,
+                  slot_map=slot_map, ln=ln, h=h, _stop=(prompt_len, stop_len, stop_tok))
 
 
 SAMPLE_MAX_TOP_K = 256  # sample.hip SMP_MAX_K
@@ -868,6 +923,44 @@ def sample_topk_topp(logits: torch.Tensor, seen: torch.Tensor, lens: torch.Tenso
                                        float(temperature), int(top_k), float(top_p), int(vocab), _p(keys_out),
                                        keys_out.stride(0), B, _stream()), "dlms_sample_topk_topp")
     return keys_out
+
+
+def logit_bans(logits: torch.Tensor, lens: torch.Tensor, finished: torch.Tensor, prompt_len: torch.Tensor,
+               out_tokens: torch.Tensor, no_repeat_ngram_size: int, min_new_tokens: int, eos: int, vocab: int,
+               slot_map: torch.Tensor | None = None) -> torch.Tensor:
+    """The bans of ``GenerationControls`` on the rows of f32 ``logits`` [B, ld], in place, between the
+    LM head and ``sample_topk_topp``: row i, whose sequence ``out_tokens[s, :lens[s]]`` lives in slot
+    s = ``slot_map[i]`` (default i), gets -inf at every token that would complete a repeated n-gram
+    (``no_repeat_ngram_size`` n > 0) and at ``eos`` while ``lens[s] - prompt_len[s] < min_new_tokens``.
+    Rows with ``finished[s]`` set are left alone; every other logit keeps its bits.  The definition:
+    ``controls.hip`` / ``models.gpt2.banned_tokens``."""
+    _req(logits, torch.float32, "logits", 2)
+    _req(lens, torch.int32, "lens", 1)
+    _req(finished, torch.int32, "finished", 1)
+    _req(prompt_len, torch.int32, "prompt_len", 1)
+    _req(out_tokens, torch.int32, "out_tokens", 2)
+    B, ld = logits.shape[0], logits.stride(0)
+    if B < 1 or not 1 <= vocab <= logits.shape[1] or logits.stride(1) != 1 or ld < vocab:
+        raise ValueError(f"logit_bans: logits {tuple(logits.shape)} (row stride {ld}) vs vocab {vocab}")
+    n, m = int(no_repeat_ngram_size), int(min_new_tokens)
+    if n < 0 or m < 0 or not 0 <= eos < vocab:
+        raise ValueError("logit_bans: no_repeat_ngram_size >= 0, min_new_tokens >= 0, 0 <= eos < vocab")
+    max_len = out_tokens.shape[1]
+    if not 1 <= max_len <= 12288 or out_tokens.stride(1) != 1 or out_tokens.stride(0) < max_len:
+        raise ValueError("logit_bans: out_tokens must be [slots, 1 .. 12288] rows")
+    nslots = B
+    if slot_map is not None:
+        _req(slot_map, torch.int32, "slot_map", 1)
+        if slot_map.numel() < B:
+            raise ValueError("slot_map too short")
+        nslots = lens.numel()  # callers guarantee every slot_map entry is < the state capacity
+    if min(lens.numel(), finished.numel(), prompt_len.numel(), out_tokens.shape[0]) < nslots:
+        raise ValueError("logit_bans: lens / finished / prompt_len / out_tokens too short")
+    _check(lib().dlms_logit_bans(_p(logits), ld, _p(lens), _p(finished), _p(prompt_len), _p(out_tokens),
+                                 out_tokens.stride(0), max_len, _p(slot_map),
+                                 min(lens.numel(), finished.numel(), prompt_len.numel(), out_tokens.shape[0]), n, m,
+                                 int(eos), int(vocab), B, _stream()), "dlms_logit_bans")
+    return logits
 
 
 def philox4x32_10(counters_keys: torch.Tensor) -> torch.Tensor:

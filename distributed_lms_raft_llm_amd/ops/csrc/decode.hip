@@ -91,6 +91,26 @@ __global__ __launch_bounds__(256) void argmax_reduce_kernel(const unsigned long 
 // last token) together with the LayerNorm weights, (3) the token's embedding row.  Every load of a
 // batch is unconditional (clamped index, value masked or unused afterwards): a load under a
 // per-lane condition is emitted as branch, load, full wait, which made each batch a chain of its own.
+//
+// STOP (GenerationControls.stop; the definition is in controls.hip): after the token is written at
+// index p the row also finishes when for a stop sequence s of length m both p + 1 - m >= P (the
+// row's prompt length: the match lies wholly in generated tokens) and seq[p+1-m : p+1] == s.  The
+// table holds STOP_MAX_SEQS sequences of up to STOP_MAX_LEN ids (length 0: unused).  Lane
+// u < 32 owns element j = u & 7 of sequence u >> 3: the table and the prompt length load with round
+// trip (1), the row's token at p + 1 - m + j (clamped; one of the last STOP_MAX_LEN - 1 tokens)
+// with prev_tok in round trip (2), and a ballot whose byte is all ones is a hit.  Everything else
+// is the code below, instruction for instruction: STOP = false is the kernel as it was.
+#define STOP_MAX_SEQS 4
+#define STOP_MAX_LEN 8
+template <bool STOP>
+struct StopArgs {};  // (an empty kernel argument: the launch of STOP = false passes what it always passed)
+template <>
+struct StopArgs<true> {
+    const int* __restrict__ prompt_len;  // [slots]
+    const int* __restrict__ stop_len;    // [STOP_MAX_SEQS]
+    const int* __restrict__ stop_tok;    // [STOP_MAX_SEQS][STOP_MAX_LEN]
+};
+template <bool STOP>
 __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long long* __restrict__ keys, int nparts,
                                                             long long sb, long long sp,
                                                             const int* __restrict__ slot_map, int* lens,
@@ -102,7 +122,7 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
                                                             int D, int eos, int t_max, int n_slots, int V,
                                                             const float* __restrict__ ln_g,
                                                             const float* __restrict__ ln_b, float eps, bf16_t* h,
-                                                            int ldh) {
+                                                            int ldh, StopArgs<STOP> st) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= B) return;
@@ -112,6 +132,12 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     const int fin = finished[b];
     unsigned long long k0[KEY_ROUND];  // in flight with lens / finished
     key_round_load(keys, i, nparts, sb, sp, lane, 0, k0);
+    int st_m = 0, st_tok = 0, st_P = 0;
+    if constexpr (STOP) {  // (indices masked to the table: lanes >= 32 repeat lanes < 32 and are not counted)
+        st_m = st.stop_len[(lane >> 3) & (STOP_MAX_SEQS - 1)];
+        st_tok = st.stop_tok[lane & (STOP_MAX_SEQS * STOP_MAX_LEN - 1)];
+        st_P = st.prompt_len[b];
+    }
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler would otherwise move them behind the wait for len0)
     // where a live row's token goes (a finished row may sit at len == max_len: not an index then)
     const int live_len = fin ? 0 : (int)dlms_idx(len0, max_len, CHK_UPDATE_LEN);
@@ -120,6 +146,13 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     // (a live row's len0 - 1 is a valid index too: read it anyway, use it only for a finished row)
     const int prev_tok = out_tokens[(size_t)b * max_len + (len0 > 0 ? len0 - 1 : 0)];
     const int last_tok = fin ? prev_tok : 0;
+    int st_at = 0, st_have = 0;  // this lane's element of its stop sequence: index in the row, the token there
+    if constexpr (STOP) {
+        st_m = st_m < 0 ? 0 : (st_m > STOP_MAX_LEN ? STOP_MAX_LEN : st_m);
+        st_at = live_len + 1 - st_m + (lane & (STOP_MAX_LEN - 1));
+        const int at = st_at < 0 ? 0 : (st_at < max_len ? st_at : max_len - 1);
+        st_have = out_tokens[(size_t)b * max_len + at];
+    }
     // the row in float4 chunks c = lane + 64 j -- add_layernorm_kernel's partition, so the fused
     // LayerNorm below computes exactly what that kernel would on the stored row; chunks past the
     // row (c >= nv) read the row's last chunk and are never used
@@ -153,12 +186,23 @@ __global__ __launch_bounds__(256) void decode_update_kernel(const unsigned long 
     } else {
         tok = (int)dlms_idx(last_tok, V, CHK_UPDATE_TOKEN);
     }
+    bool stop_hit = false;
+    if constexpr (STOP) {
+        const int j = lane & (STOP_MAX_LEN - 1);
+        // elements past the sequence's end agree; the last one is the token chosen now (index
+        // live_len, not yet in memory); the others were loaded above and lie at or past P
+        const bool ok = st_m > 0 && (j >= st_m || (live_len + 1 - st_m >= st_P &&
+                                                   (st_at == live_len ? tok : st_have) == st_tok));
+        const unsigned int hits = (unsigned int)__ballot(ok);  // lanes 0..31: a byte per sequence
+#pragma unroll
+        for (int s = 0; s < STOP_MAX_SEQS; ++s) stop_hit = stop_hit || ((hits >> (8 * s)) & 0xffu) == 0xffu;
+    }
     if (lane == 0) {
         if (!fin) {
             out_tokens[(size_t)b * max_len + live_len] = tok;
             atomicOr(seen + (size_t)b * seen_words + (tok >> 5), 1u << (tok & 31));  // no read-back wait
             lens[b] = live_len + 1;
-            if (tok == eos || live_len + 1 >= max_len) finished[b] = 1;
+            if (tok == eos || live_len + 1 >= max_len || (STOP && stop_hit)) finished[b] = 1;
         }
         cur_tok[b] = tok;
         cur_pos[b] = pos;
@@ -227,10 +271,29 @@ extern "C" hipError_t dlms_decode_update(const unsigned long long* keys, int npa
                                          const float* ln_b, float eps, void* h, int ldh, hipStream_t stream) {
     if (D % 8 != 0 || D > 64 * DU_MAXV4 * 4 || B <= 0 || nparts <= 0 || (h && (!ln_g || !ln_b || ldh % 4)))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_update_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, keys, nparts, sb, sp, slot_map,
-                       lens, finished, out_tokens, max_len, seen, seen_words, cur_tok, cur_pos, cur_kvlen,
+    hipLaunchKernelGGL(decode_update_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, stream, keys, nparts, sb, sp,
+                       slot_map, lens, finished, out_tokens, max_len, seen, seen_words, cur_tok, cur_pos, cur_kvlen,
                        reinterpret_cast<const bf16_t*>(wte), reinterpret_cast<const bf16_t*>(wpe), x, ldx, B, D, eos,
-                       t_max, n_slots, V, ln_g, ln_b, eps, reinterpret_cast<bf16_t*>(h), ldh);
+                       t_max, n_slots, V, ln_g, ln_b, eps, reinterpret_cast<bf16_t*>(h), ldh, StopArgs<false>{});
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dlms_decode_update_stop(const unsigned long long* keys, int nparts, long long sb, long long sp,
+                                              const int* slot_map, int* lens, int* finished, int* out_tokens,
+                                              int max_len, unsigned int* seen, int seen_words, int* cur_tok,
+                                              int* cur_pos, int* cur_kvlen, const void* wte, const void* wpe, float* x,
+                                              int ldx, int B, int D, int eos, int t_max, int n_slots, int V,
+                                              const float* ln_g, const float* ln_b, float eps, void* h, int ldh,
+                                              const int* prompt_len, const int* stop_len, const int* stop_tok,
+                                              hipStream_t stream) {
+    if (D % 8 != 0 || D > 64 * DU_MAXV4 * 4 || B <= 0 || nparts <= 0 || (h && (!ln_g || !ln_b || ldh % 4)) ||
+        !prompt_len || !stop_len || !stop_tok || max_len < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_update_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, stream, keys, nparts, sb, sp,
+                       slot_map, lens, finished, out_tokens, max_len, seen, seen_words, cur_tok, cur_pos, cur_kvlen,
+                       reinterpret_cast<const bf16_t*>(wte), reinterpret_cast<const bf16_t*>(wpe), x, ldx, B, D, eos,
+                       t_max, n_slots, V, ln_g, ln_b, eps, reinterpret_cast<bf16_t*>(h), ldh,
+                       StopArgs<true>{prompt_len, stop_len, stop_tok});
     return hipGetLastError();
 }
 

@@ -30,7 +30,8 @@ import torch
 
 from .. import wire
 from ..engine.scheduler import Overloaded
-from ..models.config import GenerationConfig, SamplingParams, gpt2_config
+from ..models.config import (CONTROLS_MAX_STOP, CONTROLS_MAX_STOP_LEN, GenerationConfig, GenerationControls,
+                             SamplingParams, gpt2_config)
 from ..models.gpt2 import init_gpt2_weights, load_safetensors_weights
 from ..tokenizer import GPT2BPE
 from ..utils.config import parse_with_config
@@ -136,14 +137,16 @@ class Batcher:
     def _run(self, batch: list[_Req]):
         t0 = time.perf_counter()
         try:
-            sp = self.gen.sampling()
+            sp, ct = self.gen.sampling(), self.gen.controls()
+            mode = {} if ct is None else {"controls": ct}  # (only when set: engines are called as before)
             if sp is None:
-                outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty)
+                outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty,
+                                            **mode)
             else:
                 sp = dataclasses.replace(sp, seed=(sp.seed + self.batches) % 2 ** 64)
                 self.batches += 1
                 outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty,
-                                            sampling=sp)
+                                            sampling=sp, **mode)
         except Exception as e:  # fail the whole batch, keep serving
             log.exception("generation failed")
             for r in batch:
@@ -163,6 +166,49 @@ class Batcher:
     def stop(self):
         self._stop.set()
         self._t.join(timeout=2)
+
+
+def trim_stop(out: list[int], prompt_len: int, stop) -> tuple[list[int], bool]:
+    """``out`` without the stop sequence its generated part ends with (the longest one, when one is a
+    suffix of another), and whether there was one (``models.gpt2.stop_hit``'s rule)."""
+    m = max((len(s) for s in stop if len(s) and len(out) - len(s) >= prompt_len and
+             list(out[len(out) - len(s):]) == list(s)), default=0)
+    return (list(out[: len(out) - m]), True) if m else (out, False)
+
+
+class StopTrimmer:
+    """A batcher whose results come back without the stop sequence that ended them (the servers
+    drop it before detokenising) and which counts those results; everything else is the batcher's."""
+
+    def __init__(self, batcher, stop):
+        self._batcher = batcher
+        self._stop_seqs = tuple(stop)
+        self.stopped_by_sequence = 0
+
+    def submit(self, ids: list[int]) -> futures.Future:
+        inner = self._batcher.submit(ids)
+        fut: futures.Future = futures.Future()
+        n = max(1, len(ids))  # (an empty prompt is served as one EOS token)
+
+        def done(f):
+            try:
+                out, hit = trim_stop(f.result(), n, self._stop_seqs)
+            except BaseException as e:
+                fut.set_exception(e)
+                return
+            self.stopped_by_sequence += hit
+            fut.set_result(out)
+
+        inner.add_done_callback(done)
+        return fut
+
+    def __getattr__(self, name):
+        return getattr(self._batcher, name)
+
+
+def front_batcher(batcher, controls):
+    """What the servicers submit to: ``batcher``, behind a ``StopTrimmer`` when ``controls`` has stops."""
+    return StopTrimmer(batcher, controls.stop) if controls is not None and controls.stop else batcher
 
 
 class TutoringServicer:
@@ -260,9 +306,12 @@ class TutoringServer:
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_batch: int = 64, window_ms: float = 2.0,
                  max_length: int = 150, repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None,
                  workers: int = 64, batching: str = "auto", chunk: int = 8, max_queue: int | None = None,
-                 sampling=None):
-        """``sampling`` (a ``SamplingParams``, every server class): answers are sampled, not greedy."""
-        self.gen = generation_config(max_length, repetition_penalty, sampling)
+                 sampling=None, controls=None):
+        """``sampling`` (a ``SamplingParams``, every server class): answers are sampled, not greedy.
+        ``controls`` (a ``GenerationControls``, every server class): n-gram blocking, a minimum length
+        and stop sequences; a matched stop sequence is dropped from the answer."""
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         if batching == "auto":
             batching = "continuous" if hasattr(engine, "admit") else "window"
@@ -272,14 +321,16 @@ class TutoringServer:
             if engine.max_length != max_length:
                 raise ValueError("continuous batching: engine max_length differs from the server's")
             self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                             max_queue=default_max_queue(engine, max_queue), sampling=sampling)
+                                             max_queue=default_max_queue(engine, max_queue), sampling=sampling,
+                                             **_controls_kw(controls))
         else:
             self.batcher = Batcher(engine, self.gen, max_batch=max_batch, window_ms=window_ms)
         self.batching = batching
         self.server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                                   options=[("grpc.max_send_message_length", wire.DEFAULT_MAX_MESSAGE),
                                            ("grpc.max_receive_message_length", wire.DEFAULT_MAX_MESSAGE)])
-        wire.register(self.server, "Tutoring", TutoringServicer(self.batcher, self.tok, max_length))
+        self.front = front_batcher(self.batcher, controls)
+        wire.register(self.server, "Tutoring", TutoringServicer(self.front, self.tok, max_length))
         self.engine = engine
         self._stopping = threading.Event()
         self.server.add_generic_rpc_handlers((debug_handler(health=self._health),))
@@ -303,6 +354,8 @@ class TutoringServer:
                        prefix_rows_skipped=eng.prefix_rows_skipped, prefix_decode_launches=eng.prefix_decode_launches,
                        prefix_hit_rate=round(eng.prefix_hits / n, 4) if n else None)
             METRICS.set("tutor_prefix_hit_rate", eng.prefix_hits / n if n else 0.0)
+        if getattr(self, "controls", None) is not None and self.controls.stop:
+            out.update(stopped_by_sequence=self.front.stopped_by_sequence)
         if self.batching == "continuous":
             out.update(active=b.active, completed=b.completed, ok=b._error is None and b._thread.is_alive())
         else:
@@ -375,7 +428,7 @@ class AioTutoringServer(TutoringServer):
 
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_length: int = 150,
                  repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None, chunk: int = 8,
-                 max_queue: int | None = None, sampling=None):
+                 max_queue: int | None = None, sampling=None, controls=None):
         import asyncio
 
         from ..engine.scheduler import ContinuousBatcher
@@ -384,10 +437,13 @@ class AioTutoringServer(TutoringServer):
             raise ValueError("the aio front end needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = generation_config(max_length, repetition_penalty, sampling)
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling)
+                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling,
+                                         **_controls_kw(controls))
+        self.front = front_batcher(self.batcher, controls)
         self.batching = "continuous"
         self.engine = engine
         self._stopping = threading.Event()
@@ -399,7 +455,7 @@ class AioTutoringServer(TutoringServer):
             srv = grpc.aio.server(migration_thread_pool=futures.ThreadPoolExecutor(max_workers=4),
                                   options=[("grpc.max_send_message_length", wire.DEFAULT_MAX_MESSAGE),
                                            ("grpc.max_receive_message_length", wire.DEFAULT_MAX_MESSAGE)])
-            wire.register(srv, "Tutoring", AioTutoringServicer(self.batcher, self.tok))
+            wire.register(srv, "Tutoring", AioTutoringServicer(self.front, self.tok))
             srv.add_generic_rpc_handlers((debug_handler(health=self._health),))
             return srv, srv.add_insecure_port(f"{host}:{port}")
 
@@ -434,16 +490,19 @@ class PooledTutoringServer(TutoringServer):
     stop() as ``TutoringServer``."""
 
     def __init__(self, engine, pool, max_length: int = 150, repetition_penalty: float = 1.2, chunk: int = 8,
-                 max_queue: int | None = None, sampling=None):
+                 max_queue: int | None = None, sampling=None, controls=None):
         from ..engine.scheduler import ContinuousBatcher
 
         if not hasattr(engine, "admit"):
             raise ValueError("the front-end pool needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = generation_config(max_length, repetition_penalty, sampling)
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        self.controls = controls
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
-                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling)
+                                         max_queue=default_max_queue(engine, max_queue), sampling=sampling,
+                                         **_controls_kw(controls))
+        self.front = front_batcher(self.batcher, controls)
         self.batching = "continuous"
         self.engine = engine
         self.pool = pool
@@ -451,7 +510,7 @@ class PooledTutoringServer(TutoringServer):
         self._stopping = threading.Event()
 
     def start(self, on_fatal=None, poll_s: float = 0.25):
-        self.pool.serve(self.batcher, health=self._health)
+        self.pool.serve(self.front, health=self._health)
         self.port = self.pool.port
         log.info("tutoring server on port %d (%d front-end processes)", self.port, self.pool.n)
         self._arm_fatal(on_fatal, poll_s)
@@ -468,13 +527,44 @@ class PooledTutoringServer(TutoringServer):
 EXIT_FATAL = 75  # EX_TEMPFAIL: the supervisor restarts the replica
 
 
-def generation_config(max_length: int, repetition_penalty: float, sampling=None) -> GenerationConfig:
-    """The servers' ``GenerationConfig``: greedy, or carrying ``sampling``'s fields with ``do_sample`` set."""
+def generation_config(max_length: int, repetition_penalty: float, sampling=None, controls=None) -> GenerationConfig:
+    """The servers' ``GenerationConfig``: greedy, or carrying ``sampling``'s fields with ``do_sample``
+    set; with ``controls``'s fields when given."""
+    ck = {} if controls is None else dict(no_repeat_ngram_size=controls.no_repeat_ngram_size,
+                                          min_new_tokens=controls.min_new_tokens, stop=controls.stop)
     if sampling is None:
-        return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty)
+        return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty, **ck)
     return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty, do_sample=True,
                             temperature=sampling.temperature, top_k=sampling.top_k, top_p=sampling.top_p,
-                            seed=sampling.seed)
+                            seed=sampling.seed, **ck)
+
+
+def _controls_kw(controls) -> dict:
+    return {} if controls is None else {"controls": controls}
+
+
+def decode_escapes(text: str) -> str:
+    """``text`` with its backslash escapes decoded (``\\n`` -> a newline), other characters kept."""
+    return text.encode("latin-1", "backslashreplace").decode("unicode_escape")
+
+
+def controls_from_args(args, tok=None) -> "GenerationControls | None":
+    """``--no-repeat-ngram-size / --min-new-tokens / --stop`` -> ``GenerationControls`` (None: none
+    given).  Each ``--stop`` text has its backslash escapes decoded and is encoded once with ``tok``
+    (the server's tokenizer)."""
+    texts = list(args.stop or [])
+    if not (args.no_repeat_ngram_size or args.min_new_tokens or texts):
+        return None
+    if texts and tok is None:
+        raise ValueError("--stop: a tokenizer is needed to encode the stop texts")
+    stop = []
+    for t in texts:
+        ids = tuple(int(i) for i in tok.encode(decode_escapes(t)))
+        if not ids:
+            raise ValueError(f"--stop {t!r}: encodes to no tokens")
+        stop.append(ids)
+    return GenerationControls(no_repeat_ngram_size=args.no_repeat_ngram_size, min_new_tokens=args.min_new_tokens,
+                              stop=tuple(stop))
 
 
 def sampling_from_args(args) -> "SamplingParams | None":
@@ -542,6 +632,17 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--top-k", type=int, default=50)
     ap.add_argument("--top-p", type=float, default=0.9)
     ap.add_argument("--seed", type=int, default=0, help="sampling seed (the n-th request of a run draws from stream n)")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0, metavar="N",
+                    help="no N-gram of tokens occurs twice in an answer's sequence, prompt included (0: off); with "
+                         "--min-new-tokens and --stop: bf16 weights on one GPU per replica")
+    ap.add_argument("--min-new-tokens", type=int, default=0, metavar="N",
+                    help="the end-of-text token is banned until N tokens have been generated")
+    ap.add_argument("--stop", action="append", default=None, metavar="TEXT",
+                    help="stop sequence (repeatable, at most %d of at most %d tokens): an answer ends once its "
+                         "generated tokens end with TEXT's tokens, which are dropped from it; backslash escapes are "
+                         "decoded ('\\nQuestion:' starts with a newline).  TEXT is encoded once with the server's "
+                         "tokenizer and matching is on tokens: a stop text that BPE merges with the characters "
+                         "before it will not match" % (CONTROLS_MAX_STOP, CONTROLS_MAX_STOP_LEN))
     return ap
 
 
@@ -570,7 +671,20 @@ def main(argv=None):
         why = prefix_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
         if why:
             ap.error(f"--prefix-cache on: {why}")
+    controls = None
+    if args.no_repeat_ngram_size or args.min_new_tokens or args.stop:
+        from ..engine.gpt2_engine import controls_unsupported
+
+        why = controls_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+        if why:
+            ap.error(f"--no-repeat-ngram-size / --min-new-tokens / --stop: {why}")
+        try:  # (the stop texts are encoded here, once, with the tokenizer the server detokenises with)
+            controls = controls_from_args(args, GPT2BPE(args.vocab, args.merges,
+                                                        eos_token_id=gpt2_config(args.model).eos_token_id))
+        except ValueError as e:
+            ap.error(str(e))
     mode = {} if sampling is None else {"sampling": sampling}
+    mode.update(_controls_kw(controls))
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
