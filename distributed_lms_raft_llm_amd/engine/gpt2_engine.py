@@ -219,6 +219,17 @@ def controls_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
     return None
 
 
+def logprobs_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
+    """Why an engine of this shape cannot return log-probabilities (None: it can)."""
+    if tp_size > 1:
+        return ("log-probabilities are not supported with tensor parallelism (tp_size > 1): the device log-softmax "
+                "reduces one rank's whole vocabulary; serve without logprobs or TP=1")
+    if fp8_weights:
+        return ("log-probabilities are not supported with fp8 weights: the fp8 LM head has no f32-logits epilogue "
+                "to take them from; serve without logprobs or weight_dtype='bf16'")
+    return None
+
+
 def split_prefix(prompts, prefix) -> list[int]:
     """Per prompt, the number of leading tokens the prefix cache supplies: ``len(prefix)`` when the
     prompt starts with ``prefix`` and is longer than it (at least one suffix row has to run for the
@@ -581,6 +592,11 @@ class HipGPT2Engine:
         self._controls: GenerationControls | None = None
         self.prompt_len: torch.Tensor | None = None
         self._stop_tables: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}
+        # log-probabilities (False: none) of the public call in progress (_logprobs_scope); the
+        # chosen tokens' log-probabilities [slot][position], allocated on the first such call
+        self._logprobs = False
+        self.out_logprob: torch.Tensor | None = None
+        self._lp_rows: list | None = None  # generate(logprobs=True): the rows' results while it runs
         self._alloc_state()
         self.xgmi = None
         if self.tp_size > 1:
@@ -873,7 +889,7 @@ class HipGPT2Engine:
         seen_rows = self.seen[lo:hi] if seen is None else seen
         P = self.key_parts.shape[1]  # partial keys per row the LM head writes (and the consumer reads)
         sp, ct = self._sampling, self._controls
-        if sp is None and ct is not None and ct.bans:
+        if sp is None and ((ct is not None and ct.bans) or self._logprobs):
             sp = _GREEDY_AS_SAMPLING  # the sampler's definition at top_k = 1: the largest unbanned key
         if sp is not None:
             # sampling: raw f32 logits (the GEMMs' plain f32 epilogues; the penalty moves into the
@@ -881,7 +897,8 @@ class HipGPT2Engine:
             if self._sampling is not None:
                 self._check_sampling(sp)
             if hidden.dtype == ops.FP8 or self._logits is None:
-                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope / _controls_scope")
+                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope / _controls_scope / "
+                                 "_logprobs_scope")
             z = self._logits[lo:hi]
             if self.ps_lm and B >= self.PS_LM_MIN_ROWS:
                 ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
@@ -905,6 +922,16 @@ class HipGPT2Engine:
                 ops.sample_topk_topp(z, seen_rows, self.lens, self.rng_stream, self.rng_seed, penalty,
                                      sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi],
                                      slot_map=slot_map)
+            if self._logprobs:
+                # the chosen token's log-probability into out_logprob[slot][lens[slot]]: behind the
+                # sampler, which chose it, and ahead of the update, which advances lens
+                if slot_map is None:
+                    ops.token_logprob(z, cfg.vocab_size, self.out_logprob[lo:hi], keys=self.key_parts[lo:hi],
+                                      seen=seen_rows, lens=self.lens[lo:hi], finished=self.finished[lo:hi],
+                                      penalty=penalty)
+                else:
+                    ops.token_logprob(z, cfg.vocab_size, self.out_logprob, keys=self.key_parts[lo:hi], seen=seen_rows,
+                                      lens=self.lens, finished=self.finished, penalty=penalty, slot_map=slot_map)
         elif hidden.dtype != ops.FP8 and self.ps_lm and B >= self.PS_LM_MIN_ROWS:
             P = ops.gemm_ps_key_slots(B, self.lm_head_sh.shape[0] * 16, self.lm_head_sh.shape[1] * 32)
             ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_ARGMAX, argmax_out=self.key_parts[lo:hi], seen=seen_rows,
@@ -986,6 +1013,31 @@ class HipGPT2Engine:
         finally:
             self._controls = prev
 
+    @contextlib.contextmanager
+    def _logprobs_scope(self, logprobs: bool):
+        """Whether one public call returns log-probabilities, like ``_sampling_scope``: every LM head
+        issued (or captured) inside takes the f32-logit path (greedy: the sampler at top_k = 1) and
+        records the chosen token's log-probability (``ops.token_logprob``); graphs are keyed by it.
+        False: exactly the calls made before."""
+        if logprobs:
+            why = logprobs_unsupported(self.tp_size, self.w.fp8)
+            if why:
+                raise ValueError(why)
+            # (outside any capture: graph pools must not own these)
+            if self._logits is None:
+                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
+                                           device=self.device)
+            if self.out_logprob is None:
+                self.out_logprob = torch.full((self.max_batch, self.max_length), float("nan"), dtype=torch.float32,
+                                              device=self.device)
+            if self.prompt_len is None:  # (collect cuts a slot's log-probabilities at its prompt's end)
+                self.prompt_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+        prev, self._logprobs = self._logprobs, bool(logprobs)
+        try:
+            yield
+        finally:
+            self._logprobs = prev
+
     def _check_controls(self, controls):
         if not isinstance(controls, GenerationControls):
             raise TypeError("controls: a GenerationControls (models/config.py) or None")
@@ -1021,10 +1073,13 @@ class HipGPT2Engine:
 
     def _skey(self) -> tuple:
         """What the captured graphs depend on beyond their shapes: the sampling mode, the generation
-        controls, and whether the decode attention reads the prefix store."""
+        controls, whether log-probabilities are recorded, and whether the decode attention reads the
+        prefix store."""
         key = () if self._sampling is None else self._sampling.shape_key
         if self._controls is not None:
             key = key + self._controls.shape_key
+        if self._logprobs:
+            key = key + ("logprobs",)
         return key + ("pfx",) if self._pfx_decode() else key
 
     def _overlap_ok(self, B: int) -> bool:
@@ -1096,8 +1151,9 @@ class HipGPT2Engine:
 
         # (the launch-per-op path serves row counts whose stream window outgrows the LDS ring)
         # (sampling: the dataflow kernel's LM head is greedy; launch-per-op serves those rows.
-        # Generation controls: its commit block knows none of them; the same)
-        return (self.dataflow and self._sampling is None and self._controls is None and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
+        # Generation controls: its commit block knows none of them; the same.  Log-probabilities: it
+        # never materialises logits; the same)
+        return (self.dataflow and self._sampling is None and self._controls is None and not self._logprobs and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
                 and time.monotonic() >= self._df_off_until and self._df_decoder().fits(B))
 
     def _df_run(self, B: int, steps: int, penalty: float) -> bool:
@@ -1513,8 +1569,12 @@ class HipGPT2Engine:
             self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
         ops.seen_set(self.seen, slot_d, tokens_d)
         self.lens.index_copy_(0, idx, lens_d)
-        if self._controls is not None:  # the prompts' lengths: what min_new_tokens and the stops count from
+        if self._controls is not None or self._logprobs:
+            # the prompts' lengths: what min_new_tokens and the stops count from, and where a slot's
+            # log-probabilities begin
             self.prompt_len.index_copy_(0, idx, lens_d)
+        if self._logprobs:  # (a position the decode never reaches stays NaN)
+            self.out_logprob.index_fill_(0, idx, float("nan"))
         self.finished.index_copy_(0, idx, fin_d)
         # the LM head of the first token reads the prompts' bitmaps as rows [0, n)
         seen_d = self.seen.index_select(0, idx)
@@ -1658,12 +1718,17 @@ class HipGPT2Engine:
     # ------------------------------------------------------------------ slot API (continuous batching)
     @torch.no_grad()
     def admit(self, prompts: list[list[int]], slots: list[int], repetition_penalty: float = 1.2,
-              sampling: SamplingParams | None = None, controls: GenerationControls | None = None):
+              sampling: SamplingParams | None = None, controls: GenerationControls | None = None,
+              logprobs: bool = False):
         """Prefill new sequences into free ``slots`` of the running batch (first token included).
         ``sampling``: draw their tokens instead; each takes the next stream id (the count of requests
         admitted since the seed was last set: ``reseed``, or a ``sampling.seed`` other than the
         current one).  ``controls``: the slots' generation controls; every later call that serves
-        these slots passes the same."""
+        these slots passes the same.  ``logprobs``: record the chosen tokens' log-probabilities
+        (``collect(..., logprobs=True)`` returns them); every later call passes the same too."""
+        if logprobs:
+            with self._logprobs_scope(True):
+                return self.admit(prompts, slots, repetition_penalty, sampling, controls)
         if controls is not None:
             with self._controls_scope(controls):
                 return self.admit(prompts, slots, repetition_penalty, sampling)
@@ -1673,10 +1738,14 @@ class HipGPT2Engine:
 
     @torch.no_grad()
     def decode(self, B: int, steps: int, repetition_penalty: float = 1.2, sampling: SamplingParams | None = None,
-               controls: GenerationControls | None = None):
+               controls: GenerationControls | None = None, logprobs: bool = False):
         """``steps`` decode steps over slots [0, B) (finished/inert slots are no-ops): greedy, or
         sampled with ``sampling`` under the slots' stream ids (``admit``); under ``controls``, the
-        ones the slots were admitted with."""
+        ones the slots were admitted with; with ``logprobs``, recording the chosen tokens'
+        log-probabilities, as the slots were admitted."""
+        if logprobs:
+            with self._logprobs_scope(True):
+                return self.decode(B, steps, repetition_penalty, sampling, controls)
         if controls is not None:
             with self._controls_scope(controls):
                 return self.decode(B, steps, repetition_penalty, sampling)
@@ -1706,11 +1775,15 @@ class HipGPT2Engine:
     @torch.no_grad()
     def warm_decode_graphs(self, repetition_penalty: float = 1.2, max_batch: int | None = None,
                            sampling: SamplingParams | None = None,
-                           controls: GenerationControls | None = None) -> tuple[int, float]:
+                           controls: GenerationControls | None = None, logprobs: bool = False) -> tuple[int, float]:
         """Capture the decode-step graphs ``decode()`` would capture on first use (one step and one
         replay's worth of steps per batch bucket up to ``max_batch``; the dataflow buckets need none)
         so a server's first burst of queries does not pay the captures.  ``sampling``: the graphs of
-        that sampling mode; ``controls``: of those generation controls.  Returns (graphs, seconds)."""
+        that sampling mode; ``controls``: of those generation controls; ``logprobs``: the graphs that
+        record log-probabilities.  Returns (graphs, seconds)."""
+        if logprobs:
+            with self._logprobs_scope(True):
+                return self.warm_decode_graphs(repetition_penalty, max_batch, sampling, controls)
         if controls is not None:
             with self._controls_scope(controls):
                 return self.warm_decode_graphs(repetition_penalty, max_batch, sampling)
@@ -1787,26 +1860,42 @@ class HipGPT2Engine:
         h.copy_(self.finished[:B], non_blocking=True)
         return HostResult(lambda: h.tolist(), keep=(h,))
 
-    def collect_async(self, slots: list[int]) -> "HostResult":
+    def collect_async(self, slots: list[int], logprobs: bool = False) -> "HostResult":
         """``collect`` as a copy in flight (finished sequences never change, so the tokens can be
         gathered behind a later decode chunk; a slot may be re-admitted right after, the admission
         is stream-ordered behind this copy)."""
+        if logprobs and self.out_logprob is None:
+            raise ValueError("collect: no slot was admitted with logprobs=True")
         if not slots:
-            return HostResult(lambda: [])
+            return HostResult(lambda: ([], []) if logprobs else [])
         idx = _to_device(np.asarray(slots, dtype=np.int64), self.device)
         lens_h = torch.empty(len(slots), dtype=torch.int32, pin_memory=True)
         toks_h = torch.empty(len(slots), self.max_length, dtype=torch.int32, pin_memory=True)
         lens_h.copy_(self.lens.index_select(0, idx), non_blocking=True)
         toks_h.copy_(self.out_tokens.index_select(0, idx), non_blocking=True)
+        if not logprobs:
+            def finish():
+                lens, toks = lens_h.tolist(), toks_h.tolist()
+                return [toks[i][: lens[i]] for i in range(len(slots))]
 
-        def finish():
-            lens, toks = lens_h.tolist(), toks_h.tolist()
-            return [toks[i][: lens[i]] for i in range(len(slots))]
+            return HostResult(finish, keep=(lens_h, toks_h, idx))
+        plen_h = torch.empty(len(slots), dtype=torch.int32, pin_memory=True)
+        lp_h = torch.empty(len(slots), self.max_length, dtype=torch.float32, pin_memory=True)
+        plen_h.copy_(self.prompt_len.index_select(0, idx), non_blocking=True)
+        lp_h.copy_(self.out_logprob.index_select(0, idx), non_blocking=True)
 
-        return HostResult(finish, keep=(lens_h, toks_h, idx))
+        def finish_lp():
+            lens, toks, plen, lp = lens_h.tolist(), toks_h.tolist(), plen_h.tolist(), lp_h.tolist()
+            return ([toks[i][: lens[i]] for i in range(len(slots))],
+                    [lp[i][plen[i]: lens[i]] for i in range(len(slots))])
 
-    def collect(self, slots: list[int]) -> list[list[int]]:
-        """Token sequences (prompt + generated) of ``slots``."""
+        return HostResult(finish_lp, keep=(lens_h, toks_h, plen_h, lp_h, idx))
+
+    def collect(self, slots: list[int], logprobs: bool = False):
+        """Token sequences (prompt + generated) of ``slots``; with ``logprobs`` (slots admitted with
+        it): ``(tokens, logprobs)``, one float per generated token."""
+        if logprobs:
+            return self.collect_async(slots, logprobs=True).result()
         if not slots:
             return []
         idx = torch.tensor(slots, dtype=torch.long, device=self.device)
@@ -1818,23 +1907,36 @@ class HipGPT2Engine:
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
                  stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
-                 controls: GenerationControls | None = None) -> list[list[int]]:
+                 controls: GenerationControls | None = None, logprobs: bool = False):
         """Full sequences (prompt echoed) of ``prompts``: greedy, or with ``sampling`` drawn under
         ``sampling.seed`` with prompt i on stream i -- set anew on every call, so equal calls return
         equal outputs.  ``controls`` (a ``GenerationControls``): n-gram blocking, a minimum length and
-        stop sequences, applied on the device inside the decode loop."""
+        stop sequences, applied on the device inside the decode loop.  ``logprobs``: returns
+        ``(tokens, logprobs)``; ``logprobs[i]`` holds one float per generated token of prompt i, its
+        log-probability under the distribution the repetition penalty and the bans leave
+        (``ops/csrc/logprob.hip``: at temperature 1, ahead of top-k / top-p)."""
+        if logprobs:
+            with self._logprobs_scope(True):
+                self._lp_rows = [[] for _ in prompts]
+                try:
+                    return self.generate(prompts, max_length, repetition_penalty, stats, sampling, controls), \
+                        self._lp_rows
+                finally:
+                    self._lp_rows = None
         if controls is not None:
             with self._controls_scope(controls):
                 return self.generate(prompts, max_length, repetition_penalty, stats, sampling)
         if sampling is None:
-            return self._generate(prompts, max_length, repetition_penalty, stats, None)
+            return self._generate(prompts, max_length, repetition_penalty, stats, None, list(range(len(prompts))))
         with self._sampling_scope(sampling):
             self.reseed(sampling.seed)
             self._rng_count = len(prompts)
-            return self._generate(prompts, max_length, repetition_penalty, stats, list(range(len(prompts))))
+            return self._generate(prompts, max_length, repetition_penalty, stats, list(range(len(prompts))),
+                                  list(range(len(prompts))))
 
     def _generate(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
-                  stats: GenerateStats | None, streams: list[int] | None) -> list[list[int]]:
+                  stats: GenerateStats | None, streams: list[int] | None, rows: list[int]) -> list[list[int]]:
+        """``rows``: the indices of ``prompts`` in the public call (where their log-probabilities go)."""
         T = self.max_length if max_length is None else max_length
         if T != self.max_length:
             raise ValueError(f"engine built for max_length={self.max_length}, got {T}")
@@ -1848,7 +1950,7 @@ class HipGPT2Engine:
         done, run_idx, prompts = passthrough(prompts, T, self.cfg.eos_token_id)
         if len(run_idx) < n:
             sub = self._generate([prompts[i] for i in run_idx], max_length, repetition_penalty, stats,
-                                 pick(run_idx)) if run_idx else []
+                                 pick(run_idx), [rows[i] for i in run_idx]) if run_idx else []
             for i, o in zip(run_idx, sub):
                 done[i] = o
             return done
@@ -1856,7 +1958,7 @@ class HipGPT2Engine:
             out: list[list[int]] = []
             for i in range(0, n, self.max_batch):
                 out += self._generate(prompts[i: i + self.max_batch], max_length, repetition_penalty, stats,
-                                      pick(range(i, min(n, i + self.max_batch))))
+                                      pick(range(i, min(n, i + self.max_batch))), rows[i: i + self.max_batch])
             return out
         B = min(_bucket(n), self.max_batch)  # (prompts are passthrough()'s normalised copies)
         ev0 = torch.cuda.Event(enable_timing=True)
@@ -1934,6 +2036,10 @@ class HipGPT2Engine:
         res = toks.tolist()
         for row, ln in zip(res, lens):
             del row[ln:]
+        if self._logprobs:
+            lp = self.out_logprob[:n].cpu().numpy().tolist()
+            for b in range(n):
+                self._lp_rows[rows[b]] = lp[b][len(prompts[b]): lens[b]]
         if stats is not None:
             ev2.synchronize()
             stats.batch += n
@@ -1943,6 +2049,62 @@ class HipGPT2Engine:
             stats.decode_ms += ev1.elapsed_time(ev2)
             stats.steps += steps
             stats.graph = graph is not None
+        return res
+
+    @torch.no_grad()
+    def score(self, sequences: list[list[int]]) -> list[list[float]]:
+        """Teacher-forced scoring: per sequence, the log-probabilities of its tokens 1 .. len - 1
+        given their prefixes under the model's raw distribution (no penalty, no bans, temperature
+        1: ``ops/csrc/logprob.hip`` teacher-forced mode); a one-token sequence gives ``[]``.
+        One packed prefill of the whole sequences into slots [0, n) (``n <= max_batch``, lengths
+        ``<= max_length``), ln_f of the rows that have a next token, then the f32 LM head and the
+        log-probability kernel over chunks of at most ``max_batch`` rows.  ``RuntimeError`` while any
+        slot is unfinished (the prefill overwrites the slots' K/V).  The prefix store is ignored:
+        every sequence is prefilled whole.  bf16 weights on one GPU (``logprobs_unsupported``)."""
+        cfg, dev = self.cfg, self.device
+        why = logprobs_unsupported(self.tp_size, self.w.fp8)
+        if why:
+            raise ValueError(why)
+        seqs = [[int(t) for t in s] for s in sequences]
+        n = len(seqs)
+        if n == 0:
+            return []
+        if n > self.max_batch:
+            raise ValueError(f"score: at most max_batch = {self.max_batch} sequences")
+        if min(len(s) for s in seqs) < 1 or max(len(s) for s in seqs) > self.max_length:
+            raise ValueError("score: sequence lengths must be in [1, max_length]")
+        if min(min(s) for s in seqs) < 0 or max(max(s) for s in seqs) >= cfg.vocab_size:
+            raise ValueError("score: token id out of range")
+        if int(self.finished.min().item()) == 0:
+            raise RuntimeError("score: a slot is unfinished; score between batches")
+        if self._logits is None:  # (outside any capture: graph pools must not own it)
+            self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32, device=dev)
+        tok_np, pos_np, slot_np, last_np, lens_np, sl_np = pack_prompts(seqs, list(range(n)))
+        # the packed rows that have a next token (all but each sequence's last), and that token
+        has_next = np.ones(tok_np.size, dtype=bool)
+        has_next[last_np] = False
+        rows_np = np.nonzero(has_next)[0]
+        R = rows_np.size
+        if R == 0:
+            return [[] for _ in seqs]
+        tgt_np = tok_np[rows_np + 1]
+        tokens_d, pos_d, slot_d, rows_d, tgt_d = (_to_device(a, dev) for a in (tok_np, pos_np, slot_np, rows_np, tgt_np))
+        x = self._prefill_layers(tokens_d, pos_d, slot_d, ops.AttnTiles(sl_np.tolist(), dev))
+        h = ops.layernorm_gather(x, rows_d, self.w.lnf_g, self.w.lnf_b, cfg.layer_norm_epsilon)
+        out = torch.empty(R, dtype=torch.float32, device=dev)
+        for c0 in range(0, R, self.max_batch):
+            m = min(self.max_batch, R - c0)
+            z = self._logits[:m]
+            if self.ps_lm and m >= self.PS_LM_MIN_ROWS:
+                ops.gemm_ps(h[c0:c0 + m], self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
+            else:
+                ops.gemm(h[c0:c0 + m], self.w.lm_head, ops.EPI_F32, out=z)
+            ops.token_logprob(z, cfg.vocab_size, out[c0:c0 + m], targets=tgt_d[c0:c0 + m])
+        lp = out.cpu().tolist()
+        res, o = [], 0
+        for s in seqs:
+            res.append(lp[o: o + len(s) - 1])
+            o += len(s) - 1
         return res
 
 
@@ -1963,11 +2125,19 @@ class TorchGPT2Engine:
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
                  stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
-                 controls: GenerationControls | None = None) -> list[list[int]]:
+                 controls: GenerationControls | None = None, logprobs: bool = False):
         """``sampling``: tokens drawn by ``models.gpt2.reference_sample`` under ``sampling.seed``,
         prompt i on stream i (the HIP engine's rule).  ``controls``: the bans and stops of
-        ``models.gpt2.banned_tokens`` / ``stop_hit``."""
-        from ..models.gpt2 import reference_generate
+        ``models.gpt2.banned_tokens`` / ``stop_hit``.  ``logprobs``: returns ``(tokens, logprobs)``,
+        the second from ``models.gpt2.teacher_forced_logprobs`` on the generated sequences."""
+        from ..models.gpt2 import reference_generate, teacher_forced_logprobs
+
+        if logprobs:
+            norm = passthrough(prompts, self.max_length if max_length is None else max_length,
+                               self.cfg.eos_token_id)[2]
+            outs = self.generate(prompts, max_length, repetition_penalty, stats, sampling, controls)
+            return outs, [teacher_forced_logprobs(self.model, o, len(p), repetition_penalty, controls).tolist()
+                          for o, p in zip(outs, norm)]
 
         T = self.max_length if max_length is None else max_length
         out, run_idx, norm = passthrough(prompts, T, self.cfg.eos_token_id)
@@ -1985,3 +2155,11 @@ class TorchGPT2Engine:
             stats.new_tokens += sum(len(o) - len(p) for o, p in zip(out_run, prompts))
             stats.decode_ms += (time.perf_counter() - t0) * 1e3
         return out
+
+    @torch.no_grad()
+    def score(self, sequences: list[list[int]]) -> list[list[float]]:
+        """``HipGPT2Engine.score`` on the reference model: ``models.gpt2.reference_logprob`` (no
+        penalty, no seen set) of tokens 1 .. len - 1 of each sequence, one forward per sequence."""
+        from ..models.gpt2 import teacher_forced_logprobs
+
+        return [teacher_forced_logprobs(self.model, [int(t) for t in s], 1, 1.0).tolist() for s in sequences]

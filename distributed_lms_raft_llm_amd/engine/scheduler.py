@@ -21,9 +21,11 @@ Engine protocol (``HipGPT2Engine`` implements it; tests use a CPU fake):
     admit(prompts, slots, repetition_penalty)   prefill + first token into those slots
     decode(B, steps, repetition_penalty)        ``steps`` decode steps over slots [0, B)
                                                 (both with ``sampling=`` when the batcher samples and
-                                                ``controls=`` when it has generation controls)
+                                                ``controls=`` when it has generation controls,
+                                                ``logprobs=True`` when it returns log-probabilities)
     finished_flags(B) -> list[int]              per-slot stop flags
-    collect(slots) -> list[list[int]]           prompt + generated tokens
+    collect(slots) -> list[list[int]]           prompt + generated tokens (``logprobs=True``, only
+                                                then passed: ``(tokens, logprobs)``)
     flags_async(B), collect_async(slots)        optional: the same as handles with .result()
 """
 from __future__ import annotations
@@ -70,9 +72,9 @@ class PeerStalled(RuntimeError):
     """A tensor-parallel peer never reached a collective: the affected chunk's tokens are garbage."""
 
 
-def collect_async(eng, slots: list[int]):
+def collect_async(eng, slots: list[int], **mode):
     f = getattr(eng, "collect_async", None)
-    return f(slots) if f is not None else _Ready(eng.collect(slots))
+    return f(slots, **mode) if f is not None else _Ready(eng.collect(slots, **mode))
 
 
 @dataclass
@@ -93,20 +95,25 @@ class Overloaded(RuntimeError):
 class ContinuousBatcher:
     def __init__(self, engine, repetition_penalty: float = 1.2, chunk: int = 8, max_admit: int | None = None,
                  name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0, sampling=None,
-                 controls=None):
+                 controls=None, logprobs: bool = False):
         """``max_queue``: queries allowed to wait for a free KV slot before ``submit`` raises
         ``Overloaded`` (0 = unbounded; the tutoring servers default to one batch of slots).
         ``sampling`` (a ``SamplingParams``): tokens are drawn instead of greedy; it is forwarded to
         the engine's ``admit`` / ``decode`` as ``sampling=`` -- only when set, so greedy engines are
         called exactly as before.  ``controls`` (a ``GenerationControls``): n-gram blocking, a minimum
         length and stop sequences, forwarded the same way as ``controls=`` (results keep their stop
-        tokens, as they keep EOS)."""
+        tokens, as they keep EOS).  ``logprobs``: every future resolves to ``(tokens, logprobs)``,
+        one float per generated token; forwarded as ``logprobs=True`` the same way, to ``collect`` /
+        ``collect_async`` too."""
         self.engine = engine
         self.sampling = sampling
         self.controls = controls
         self._mode = {} if sampling is None else {"sampling": sampling}
         if controls is not None:
             self._mode["controls"] = controls
+        self.logprobs = bool(logprobs)
+        self._collect_mode = {"logprobs": True} if self.logprobs else {}
+        self._mode.update(self._collect_mode)
         self.max_queue = int(max_queue or 0)
         self.rejected = 0
         env_prio = os.environ.get("DLMS_BATCHER_STREAM_PRIORITY")
@@ -149,7 +156,7 @@ class ContinuousBatcher:
         eos, T = self.engine.cfg.eos_token_id, self.engine.max_length
         p = list(prompt) if len(prompt) else [eos]
         if len(p) >= T:  # nothing to generate (generate() pass-through semantics)
-            fut.set_result(p)
+            fut.set_result((p, []) if self.logprobs else p)
             return fut
         with self._cv:
             if self._stop:
@@ -297,7 +304,7 @@ class ContinuousBatcher:
                 # by identity: a slot retired one chunk earlier may already hold a new request
                 done = [s for s, r in prev[1].items() if s < len(flags) and flags[s] and self._active.get(s) is r]
                 if done:
-                    handle = collect_async(eng, done)
+                    handle = collect_async(eng, done, **self._collect_mode)
                     with self._cv:
                         reqs = [(s, self._active.pop(s)) for s in done]
                         for s in done:
@@ -309,8 +316,11 @@ class ContinuousBatcher:
 
     def _retire(self, reqs, handle):
         outs = handle.result()
+        lps = None
+        if self.logprobs:
+            outs, lps = outs
         now = time.perf_counter()
-        for (s, r), out in zip(reqs, outs):
+        for i, ((s, r), out) in enumerate(zip(reqs, outs)):
             self.completed += 1
             n_new = len(out) - len(r.prompt)
             METRICS.observe(f"{self.name}_request_ms", (now - r.t_submit) * 1e3)
@@ -318,4 +328,4 @@ class ContinuousBatcher:
                 METRICS.observe(f"{self.name}_tpot_ms", (now - r.t_first) * 1e3 / (n_new - 1))
             METRICS.inc(f"{self.name}_tokens", n_new)
             if not r.future.done():
-                r.future.set_result(out)
+                r.future.set_result(out if lps is None else (out, lps[i]))

@@ -194,7 +194,8 @@ class GenerationConfig:
     ``sampling()`` gives the ``SamplingParams`` (``temperature``/``top_k``/``top_p`` and
     ``seed``) that the engines, the scheduler and the tutor server take as ``sampling=``.
     ``controls()`` gives the ``GenerationControls`` (``no_repeat_ngram_size``, ``min_new_tokens``,
-    ``stop``) they take as ``controls=``, or None when all three are off.
+    ``stop``) they take as ``controls=``, or None when all three are off.  ``logprobs``: generation
+    returns the chosen tokens' log-probabilities beside the tokens (``logprobs=True`` there).
     """
 
     max_length: int = 150  # total length, prompt included
@@ -215,6 +216,7 @@ class GenerationConfig:
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0
     stop: tuple = ()
+    logprobs: bool = False
 
     def controls(self) -> "GenerationControls | None":
         if not (self.no_repeat_ngram_size or self.min_new_tokens or self.stop):

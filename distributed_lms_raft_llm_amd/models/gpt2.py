@@ -648,3 +648,77 @@ def teacher_forced_sampling_check(model: GPT2Reference, seq: list[int], prompt_l
         elif top_p < 1.0 and mass[j] >= top_p * math.exp(2 * eps / T):
             out["mismatches"].append((prompt_len + j, seq[prompt_len + j], "outside nucleus", mass[j]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Log-probabilities: the normative CPU definition of ops/csrc/logprob.hip
+# ---------------------------------------------------------------------------------------------
+def reference_logprob(logits_f32, seen, penalty: float, token=None):
+    """The log-probability of ``token`` under the distribution that the logits processors leave of
+    the ``vocab`` float32 logits of a row (banned columns hold -inf), at temperature 1, ahead of
+    top-k / top-p, exactly as ``logprob.hip`` defines it: with the float32 penalised logits l_j
+    (``penalised_logits_f32``) and m = max l_j, ``(l_tok - m) - log(sum_j exp(l_j - m))`` in numpy
+    float64.  ``seen``: bool [vocab] (None: no column seen).  ``token`` None: every token's
+    log-probability, float64 [vocab]."""
+    import numpy as np
+
+    z = np.ascontiguousarray(logits_f32, dtype=np.float32)
+    l = penalised_logits_f32(z, np.zeros(z.shape, dtype=bool) if seen is None else seen, penalty).astype(np.float64)
+    m = l.max()
+    with np.errstate(divide="ignore"):
+        lp = (l - m) - np.log(np.exp(l - m).sum())
+    return lp if token is None else float(lp[int(token)])
+
+
+@torch.no_grad()
+def teacher_forced_logprobs(model: GPT2Reference, seq: list[int], prompt_len: int, repetition_penalty: float = 1.2,
+                            controls=None, eos_token_id: int | None = None):
+    """``reference_logprob`` of every generated token of ``seq`` (float64 [len(seq) - prompt_len]):
+    one forward of ``model`` over ``seq`` (teacher forcing); position j sees the float32 logits that
+    predict ``seq[prompt_len + j]``, with the bans of ``controls`` stored as -inf as
+    ``reference_generate`` applies them, and the tokens before it as the seen set."""
+    import numpy as np
+
+    cfg, dev = model.cfg, model.device
+    S = len(seq)
+    if S <= prompt_len:
+        return np.zeros(0, dtype=np.float64)
+    eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+    cache = KVCache.allocate(cfg, 1, S, dtype=model.dtype, device=dev)
+    toks = torch.tensor([seq], device=dev)
+    pos = torch.arange(S, device=dev)[None]
+    hidden = model.forward(toks, pos, cache, torch.zeros(1, dtype=torch.long, device=dev))[0]
+    logits = model.logits(hidden[prompt_len - 1: S - 1]).float().cpu().numpy()  # row j predicts seq[prompt_len + j]
+    out = np.empty(S - prompt_len, dtype=np.float64)
+    seen = np.zeros(cfg.vocab_size, dtype=bool)
+    seen[np.asarray(seq[:prompt_len], dtype=np.int64)] = True
+    for j in range(S - prompt_len):
+        if controls is not None and controls.bans:
+            ban = banned_tokens(seq[: prompt_len + j], prompt_len, controls, eos)
+            if ban:
+                logits[j, np.asarray(ban, dtype=np.int64)] = -np.inf
+        out[j] = reference_logprob(logits[j], seen, repetition_penalty, seq[prompt_len + j])
+        seen[seq[prompt_len + j]] = True
+    return out
+
+
+@torch.no_grad()
+def logprob_noise(cfg: GPT2Config, weights: dict[str, torch.Tensor], prompts: list[list[int]], max_length: int,
+                  penalty: float = 1.2, kv_dtype: str = "bf16") -> float:
+    """The largest difference between ``teacher_forced_logprobs`` of the fp32 reference and of the
+    same reference with the activations a bf16 engine rounds rounded to bf16 (``act_dtype``), over
+    the fp32 reference's own greedy generations of ``prompts``: what rounding the activations alone
+    moves a log-probability by.  From the reference alone, on the CPU, like ``kv_fp8_margin``; the
+    tests hold an engine's log-probabilities to a multiple of it."""
+    import numpy as np
+
+    exact = GPT2Reference(cfg, weights, kv_dtype=kv_dtype)
+    noisy = GPT2Reference(cfg, weights, kv_dtype=kv_dtype, act_dtype=torch.bfloat16)
+    seqs = reference_generate(exact, prompts, max_length=max_length, repetition_penalty=penalty)
+    dev = 0.0
+    for s, p in zip(seqs, prompts):
+        if len(s) > len(p):
+            a = teacher_forced_logprobs(exact, s, len(p), penalty)
+            b = teacher_forced_logprobs(noisy, s, len(p), penalty)
+            dev = max(dev, float(np.abs(a - b).max()))
+    return dev

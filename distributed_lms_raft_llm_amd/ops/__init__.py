@@ -27,14 +27,15 @@ LIB_DIR = _HERE / "_lib"
 LIB_PATH = LIB_DIR / "libdlms_hip.so"
 # debug variant: device-side range checks on every data-dependent index (common.h, DLMS_DEVICE_CHECKS)
 CHECKED_LIB_PATH = LIB_DIR / "libdlms_hip_checked.so"
-CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "sample", "controls")
+CHECK_UNITS = ("gemm", "attention", "decode", "encoder", "skinny", "gemm_ps", "sample", "controls", "logprob")
 CHECK_SITES = {1: "embed token id", 2: "position id", 3: "decode_update slot_map", 4: "decode_update token id",
                5: "decode_update sequence length", 6: "seen_set row", 7: "QKV scatter slot", 8: "QKV scatter position",
                9: "attention slot", 10: "BERT token id", 11: "seen_set token id", 12: "sampler slot_map",
                13: "sampled token id", 14: "prefix fill slot", 15: "prefix fill length",
-               16: "attention prefix length", 17: "logit_bans slot_map", 18: "logit_bans sequence length"}
+               16: "attention prefix length", 17: "logit_bans slot_map", 18: "logit_bans sequence length",
+               19: "token_logprob slot_map", 20: "token_logprob sequence length", 21: "token_logprob token id"}
 SOURCES = ["api.hip", "gemm.hip", "norm.hip", "attention.hip", "decode.hip", "encoder.hip", "xgmi.hip", "skinny.hip", "gemm_ps.hip",
-           "dataflow.hip", "mid.hip", "sample.hip", "controls.hip"]
+           "dataflow.hip", "mid.hip", "sample.hip", "controls.hip", "logprob.hip"]
 ARCH = os.environ.get("DLMS_OFFLOAD_ARCH", "gfx950")
 
 EPI_BF16, EPI_GELU_TANH, EPI_GELU_ERF, EPI_F32, EPI_QKV, EPI_ARGMAX, EPI_PARTIAL = range(7)
@@ -185,6 +186,8 @@ def _bind(L):
                                   P, ctypes.c_longlong, I, P],
         "dlms_philox4x32_10": [P, P, I, P],
         "dlms_logit_bans": [P, ctypes.c_longlong, P, P, P, P, ctypes.c_longlong, I, P, I, I, I, I, I, I, P],
+        "dlms_token_logprob": [P, ctypes.c_longlong, P, I, P, ctypes.c_longlong, P, P, P, P, I, F, I, I, P,
+                               ctypes.c_longlong, I, P],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -961,6 +964,61 @@ def logit_bans(logits: torch.Tensor, lens: torch.Tensor, finished: torch.Tensor,
                                  min(lens.numel(), finished.numel(), prompt_len.numel(), out_tokens.shape[0]), n, m,
                                  int(eos), int(vocab), B, _stream()), "dlms_logit_bans")
     return logits
+
+
+def token_logprob(logits: torch.Tensor, vocab: int, out: torch.Tensor, keys: torch.Tensor | None = None,
+                  seen: torch.Tensor | None = None, lens: torch.Tensor | None = None,
+                  finished: torch.Tensor | None = None, penalty: float = 1.0,
+                  slot_map: torch.Tensor | None = None, targets: torch.Tensor | None = None) -> torch.Tensor:
+    """The log-probability of one token per row of f32 ``logits`` [B, ld] (columns >= ``vocab``
+    ignored; -inf columns count for nothing) under the distribution the repetition penalty leaves,
+    at temperature 1.  The definition: ``logprob.hip`` / ``models.gpt2.reference_logprob``.
+    Decode mode (``keys``, ``seen``, ``lens``, ``finished``): between ``sample_topk_topp`` and
+    ``decode_update`` -- row i's token is the low word ``~tok`` of ``keys[i, 0]``, its slot
+    s = ``slot_map[i]`` (default i); the value goes to ``out[s, lens[s]]`` (f32 [slots, max_length]);
+    a finished slot, or one with ``lens[s] >= max_length``, is left alone.
+    Teacher-forced mode (``targets`` int32 [B]): row i's token is ``targets[i]``, no bitmap and no
+    penalty; the value goes to ``out[i]`` (f32 [B])."""
+    _req(logits, torch.float32, "logits", 2)
+    _req(out, torch.float32, "out")
+    B, ld = logits.shape[0], logits.stride(0)
+    if B < 1 or not 1 <= vocab <= min(logits.shape[1], 65536) or ld % 4 or logits.data_ptr() % 16 or ld > 65536:
+        raise ValueError(f"token_logprob: logits {tuple(logits.shape)} (row stride {ld}) vs vocab {vocab}")
+    if targets is not None:
+        if keys is not None or seen is not None or lens is not None or finished is not None or \
+                slot_map is not None or penalty != 1.0:
+            raise ValueError("token_logprob: targets (teacher-forced mode) takes no keys, state, slot_map or penalty")
+        _req(targets, torch.int32, "targets", 1)
+        if targets.numel() < B or out.dim() != 1 or out.numel() < B:
+            raise ValueError("token_logprob: targets / out shorter than the rows")
+        _check(lib().dlms_token_logprob(_p(logits), ld, None, 0, None, 0, _p(targets), None, None, None, 0, 1.0,
+                                        int(vocab), 0, _p(out), 0, B, _stream()), "dlms_token_logprob")
+        return out
+    if keys is None or seen is None or lens is None or finished is None:
+        raise ValueError("token_logprob: decode mode needs keys, seen, lens and finished (or pass targets)")
+    _req(keys, torch.int64, "keys", 2)
+    _req(seen, torch.int32, "seen", 2)
+    _req(lens, torch.int32, "lens", 1)
+    _req(finished, torch.int32, "finished", 1)
+    if seen.shape[0] < B or seen.shape[1] * 32 < vocab or seen.stride(0) != seen.shape[1]:
+        raise ValueError("token_logprob: seen must be contiguous [>= B, >= vocab / 32] rows")
+    if keys.shape[0] < B or keys.shape[1] < 1 or not penalty > 0:
+        raise ValueError("token_logprob: keys too small, or penalty <= 0")
+    if out.dim() != 2 or out.shape[1] < 1 or out.stride(0) < out.shape[1]:
+        raise ValueError("token_logprob: out must be [slots, max_length] rows")
+    nslots = B
+    if slot_map is not None:
+        _req(slot_map, torch.int32, "slot_map", 1)
+        if slot_map.numel() < B:
+            raise ValueError("slot_map too short")
+        nslots = lens.numel()  # callers guarantee every slot_map entry is < the state capacity
+    if min(lens.numel(), finished.numel(), out.shape[0]) < nslots:
+        raise ValueError("token_logprob: lens / finished / out too short")
+    _check(lib().dlms_token_logprob(_p(logits), ld, _p(seen), seen.stride(0), _p(keys), keys.stride(0), None,
+                                    _p(lens), _p(finished), _p(slot_map),
+                                    min(lens.numel(), finished.numel(), out.shape[0]), float(penalty), int(vocab),
+                                    out.shape[1], _p(out), out.stride(0), B, _stream()), "dlms_token_logprob")
+    return out
 
 
 def philox4x32_10(counters_keys: torch.Tensor) -> torch.Tensor:

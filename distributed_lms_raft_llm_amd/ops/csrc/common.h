@@ -306,7 +306,8 @@ enum {
     CHK_EMBED_TOKEN = 1, CHK_EMBED_POS = 2, CHK_UPDATE_SLOT = 3, CHK_UPDATE_TOKEN = 4, CHK_UPDATE_LEN = 5,
     CHK_SEEN_ROW = 6, CHK_QKV_SLOT = 7, CHK_QKV_POS = 8, CHK_ATTN_SLOT = 9, CHK_BERT_TOKEN = 10,
     CHK_SEEN_TOKEN = 11, CHK_SAMPLE_SLOT = 12, CHK_SAMPLE_TOKEN = 13, CHK_PFX_SLOT = 14, CHK_PFX_LEN = 15,
-    CHK_ATTN_PFX = 16, CHK_BANS_SLOT = 17, CHK_BANS_LEN = 18,
+    CHK_ATTN_PFX = 16, CHK_BANS_SLOT = 17, CHK_BANS_LEN = 18, CHK_LOGPROB_SLOT = 19, CHK_LOGPROB_LEN = 20,
+    CHK_LOGPROB_TOKEN = 21,
 };
 
 struct DlmsCheckRecord {

@@ -139,6 +139,8 @@ class Batcher:
         try:
             sp, ct = self.gen.sampling(), self.gen.controls()
             mode = {} if ct is None else {"controls": ct}  # (only when set: engines are called as before)
+            if self.gen.logprobs:
+                mode["logprobs"] = True
             if sp is None:
                 outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty,
                                             **mode)
@@ -152,6 +154,9 @@ class Batcher:
             for r in batch:
                 r.fut.set_exception(e)
             return
+        lps = None
+        if self.gen.logprobs:
+            outs, lps = outs
         dt = time.perf_counter() - t0
         new = sum(len(o) - len(r.ids) for o, r in zip(outs, batch))
         METRICS.observe("tutor_batch_size", len(batch))
@@ -159,9 +164,9 @@ class Batcher:
         METRICS.inc("tutor_tokens_generated", new)
         METRICS.set("tutor_tokens_per_s", new / dt if dt > 0 else 0.0)
         now = time.perf_counter()
-        for o, r in zip(outs, batch):
+        for i, (o, r) in enumerate(zip(outs, batch)):
             METRICS.observe("tutor_query_ms", (now - r.t0) * 1e3)
-            r.fut.set_result(o)
+            r.fut.set_result(o if lps is None else (o, lps[i]))
 
     def stop(self):
         self._stop.set()
@@ -178,7 +183,9 @@ def trim_stop(out: list[int], prompt_len: int, stop) -> tuple[list[int], bool]:
 
 class StopTrimmer:
     """A batcher whose results come back without the stop sequence that ended them (the servers
-    drop it before detokenising) and which counts those results; everything else is the batcher's."""
+    drop it before detokenising) and which counts those results; everything else is the batcher's.
+    A ``(tokens, logprobs)`` result (a batcher with ``logprobs=True``) loses the stop tokens'
+    log-probabilities with the tokens."""
 
     def __init__(self, batcher, stop):
         self._batcher = batcher
@@ -192,7 +199,13 @@ class StopTrimmer:
 
         def done(f):
             try:
-                out, hit = trim_stop(f.result(), n, self._stop_seqs)
+                res = f.result()
+                if isinstance(res, tuple):
+                    toks, lps = res
+                    out, hit = trim_stop(toks, n, self._stop_seqs)
+                    out = (out, list(lps[: len(lps) - (len(toks) - len(out))]))
+                else:
+                    out, hit = trim_stop(res, n, self._stop_seqs)
             except BaseException as e:
                 fut.set_exception(e)
                 return
@@ -206,9 +219,56 @@ class StopTrimmer:
         return getattr(self._batcher, name)
 
 
-def front_batcher(batcher, controls):
-    """What the servicers submit to: ``batcher``, behind a ``StopTrimmer`` when ``controls`` has stops."""
-    return StopTrimmer(batcher, controls.stop) if controls is not None and controls.stop else batcher
+class LogprobMeter:
+    """In front of a batcher whose results are ``(tokens, logprobs)``: hands on the tokens alone (the
+    answers and the wire format are those of a server without ``--logprobs``) and keeps the running
+    mean, over the answered queries, of an answer's mean token log-probability; with ``threshold``
+    also the count of answers whose mean lies below it.  Everything else is the batcher's."""
+
+    def __init__(self, batcher, threshold: float | None = None):
+        self._batcher = batcher
+        self.threshold = threshold
+        self._lock = threading.Lock()
+        self.answers = 0
+        self._sum = 0.0
+        self.low_confidence_answers = 0
+
+    @property
+    def mean_token_logprob(self) -> float | None:
+        with self._lock:
+            return self._sum / self.answers if self.answers else None
+
+    def submit(self, ids: list[int]) -> futures.Future:
+        inner = self._batcher.submit(ids)
+        fut: futures.Future = futures.Future()
+
+        def done(f):
+            try:
+                toks, lps = f.result()
+            except BaseException as e:
+                fut.set_exception(e)
+                return
+            if lps:  # (an answer of no tokens has no mean)
+                mean = sum(lps) / len(lps)
+                with self._lock:
+                    self.answers += 1
+                    self._sum += mean
+                    if self.threshold is not None and mean < self.threshold:
+                        self.low_confidence_answers += 1
+            fut.set_result(toks)
+
+        inner.add_done_callback(done)
+        return fut
+
+    def __getattr__(self, name):
+        return getattr(self._batcher, name)
+
+
+def front_batcher(batcher, controls, logprobs: bool = False, min_mean_logprob: float | None = None):
+    """What the servicers submit to: ``batcher``, behind a ``StopTrimmer`` when ``controls`` has stops,
+    and a ``LogprobMeter`` when it returns log-probabilities."""
+    front = StopTrimmer(batcher, controls.stop) if controls is not None and controls.stop else batcher
+    return LogprobMeter(front, min_mean_logprob) if logprobs else front
 
 
 class TutoringServicer:
@@ -306,11 +366,15 @@ class TutoringServer:
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_batch: int = 64, window_ms: float = 2.0,
                  max_length: int = 150, repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None,
                  workers: int = 64, batching: str = "auto", chunk: int = 8, max_queue: int | None = None,
-                 sampling=None, controls=None):
+                 sampling=None, controls=None, logprobs: bool = False, min_mean_logprob: float | None = None):
         """``sampling`` (a ``SamplingParams``, every server class): answers are sampled, not greedy.
         ``controls`` (a ``GenerationControls``, every server class): n-gram blocking, a minimum length
-        and stop sequences; a matched stop sequence is dropped from the answer."""
-        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        and stop sequences; a matched stop sequence is dropped from the answer.  ``logprobs`` (every
+        server class): the engine returns the tokens' log-probabilities and the health record gains
+        ``mean_token_logprob``; ``min_mean_logprob`` (implies it): also ``low_confidence_answers``.
+        The answers are unchanged."""
+        logprobs = bool(logprobs) or min_mean_logprob is not None
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         if batching == "auto":
@@ -322,14 +386,14 @@ class TutoringServer:
                 raise ValueError("continuous batching: engine max_length differs from the server's")
             self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                              max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                             **_controls_kw(controls))
+                                             **_controls_kw(controls), **_logprobs_kw(logprobs))
         else:
             self.batcher = Batcher(engine, self.gen, max_batch=max_batch, window_ms=window_ms)
         self.batching = batching
         self.server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                                   options=[("grpc.max_send_message_length", wire.DEFAULT_MAX_MESSAGE),
                                            ("grpc.max_receive_message_length", wire.DEFAULT_MAX_MESSAGE)])
-        self.front = front_batcher(self.batcher, controls)
+        self.front = front_batcher(self.batcher, controls, logprobs, min_mean_logprob)
         wire.register(self.server, "Tutoring", TutoringServicer(self.front, self.tok, max_length))
         self.engine = engine
         self._stopping = threading.Event()
@@ -356,6 +420,8 @@ class TutoringServer:
             METRICS.set("tutor_prefix_hit_rate", eng.prefix_hits / n if n else 0.0)
         if getattr(self, "controls", None) is not None and self.controls.stop:
             out.update(stopped_by_sequence=self.front.stopped_by_sequence)
+        if isinstance(self.front, LogprobMeter):
+            out.update(logprob_stats(self.front))
         if self.batching == "continuous":
             out.update(active=b.active, completed=b.completed, ok=b._error is None and b._thread.is_alive())
         else:
@@ -428,7 +494,8 @@ class AioTutoringServer(TutoringServer):
 
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_length: int = 150,
                  repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None, chunk: int = 8,
-                 max_queue: int | None = None, sampling=None, controls=None):
+                 max_queue: int | None = None, sampling=None, controls=None, logprobs: bool = False,
+                 min_mean_logprob: float | None = None):
         import asyncio
 
         from ..engine.scheduler import ContinuousBatcher
@@ -437,13 +504,14 @@ class AioTutoringServer(TutoringServer):
             raise ValueError("the aio front end needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        logprobs = bool(logprobs) or min_mean_logprob is not None
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                          max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                         **_controls_kw(controls))
-        self.front = front_batcher(self.batcher, controls)
+                                         **_controls_kw(controls), **_logprobs_kw(logprobs))
+        self.front = front_batcher(self.batcher, controls, logprobs, min_mean_logprob)
         self.batching = "continuous"
         self.engine = engine
         self._stopping = threading.Event()
@@ -490,19 +558,21 @@ class PooledTutoringServer(TutoringServer):
     stop() as ``TutoringServer``."""
 
     def __init__(self, engine, pool, max_length: int = 150, repetition_penalty: float = 1.2, chunk: int = 8,
-                 max_queue: int | None = None, sampling=None, controls=None):
+                 max_queue: int | None = None, sampling=None, controls=None, logprobs: bool = False,
+                 min_mean_logprob: float | None = None):
         from ..engine.scheduler import ContinuousBatcher
 
         if not hasattr(engine, "admit"):
             raise ValueError("the front-end pool needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        self.gen = generation_config(max_length, repetition_penalty, sampling, controls)
+        logprobs = bool(logprobs) or min_mean_logprob is not None
+        self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                          max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                         **_controls_kw(controls))
-        self.front = front_batcher(self.batcher, controls)
+                                         **_controls_kw(controls), **_logprobs_kw(logprobs))
+        self.front = front_batcher(self.batcher, controls, logprobs, min_mean_logprob)
         self.batching = "continuous"
         self.engine = engine
         self.pool = pool
@@ -527,11 +597,14 @@ class PooledTutoringServer(TutoringServer):
 EXIT_FATAL = 75  # EX_TEMPFAIL: the supervisor restarts the replica
 
 
-def generation_config(max_length: int, repetition_penalty: float, sampling=None, controls=None) -> GenerationConfig:
+def generation_config(max_length: int, repetition_penalty: float, sampling=None, controls=None,
+                      logprobs: bool = False) -> GenerationConfig:
     """The servers' ``GenerationConfig``: greedy, or carrying ``sampling``'s fields with ``do_sample``
-    set; with ``controls``'s fields when given."""
+    set; with ``controls``'s fields when given, and the ``logprobs`` flag."""
     ck = {} if controls is None else dict(no_repeat_ngram_size=controls.no_repeat_ngram_size,
                                           min_new_tokens=controls.min_new_tokens, stop=controls.stop)
+    if logprobs:
+        ck["logprobs"] = True
     if sampling is None:
         return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty, **ck)
     return GenerationConfig(max_length=max_length, repetition_penalty=repetition_penalty, do_sample=True,
@@ -541,6 +614,19 @@ def generation_config(max_length: int, repetition_penalty: float, sampling=None,
 
 def _controls_kw(controls) -> dict:
     return {} if controls is None else {"controls": controls}
+
+
+def _logprobs_kw(logprobs) -> dict:
+    return {"logprobs": True} if logprobs else {}
+
+
+def logprob_stats(meter: "LogprobMeter") -> dict:
+    """The health record's (and the exit line's) log-probability fields."""
+    m = meter.mean_token_logprob
+    out = {"mean_token_logprob": None if m is None else round(m, 4)}
+    if meter.threshold is not None:
+        out["low_confidence_answers"] = meter.low_confidence_answers
+    return out
 
 
 def decode_escapes(text: str) -> str:
@@ -643,6 +729,14 @@ def arg_parser() -> argparse.ArgumentParser:
                          "decoded ('\\nQuestion:' starts with a newline).  TEXT is encoded once with the server's "
                          "tokenizer and matching is on tokens: a stop text that BPE merges with the characters "
                          "before it will not match" % (CONTROLS_MAX_STOP, CONTROLS_MAX_STOP_LEN))
+    ap.add_argument("--logprobs", action="store_true",
+                    help="have the engine return every generated token's log-probability: the health record and "
+                         "the exit line gain mean_token_logprob, the running mean over the answered queries of an "
+                         "answer's mean token log-probability; the answers are unchanged; bf16 weights on one GPU "
+                         "per replica")
+    ap.add_argument("--min-mean-logprob", type=float, default=None, metavar="X",
+                    help="implies --logprobs: also count the answers whose mean token log-probability is below X "
+                         "(low_confidence_answers)")
     return ap
 
 
@@ -683,8 +777,17 @@ def main(argv=None):
                                                         eos_token_id=gpt2_config(args.model).eos_token_id))
         except ValueError as e:
             ap.error(str(e))
+    logprobs = args.logprobs or args.min_mean_logprob is not None
+    if logprobs:
+        from ..engine.gpt2_engine import logprobs_unsupported
+
+        why = logprobs_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+        if why:
+            ap.error(f"--logprobs / --min-mean-logprob: {why}")
     mode = {} if sampling is None else {"sampling": sampling}
     mode.update(_controls_kw(controls))
+    mode.update(_logprobs_kw(logprobs))
+    srv_mode = dict(mode, min_mean_logprob=args.min_mean_logprob) if logprobs else mode
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -749,7 +852,7 @@ def main(argv=None):
         log.info("captured %d decode graphs (batch buckets <= %d) in %.1f s", n, args.warm_batch, secs)
     if pool is not None and hasattr(eng, "admit"):
         srv = PooledTutoringServer(eng, pool, args.max_length, args.repetition_penalty, chunk=args.chunk,
-                                   max_queue=args.max_queue, **mode)
+                                   max_queue=args.max_queue, **srv_mode)
         if args.serve_gate:
             pool.gate_worker = make_gate_worker(args.gate_model, args.gate_weights, getattr(eng, "device", "cpu"))
             pool.gate_worker.attach(srv.batcher)
@@ -761,11 +864,11 @@ def main(argv=None):
         pass
     elif args.frontend == "aio" and args.batching != "window" and hasattr(eng, "admit"):
         srv = AioTutoringServer(eng, args.port, args.host, args.max_length, args.repetition_penalty, tokenizer=tok,
-                                chunk=args.chunk, max_queue=args.max_queue, **mode)
+                                chunk=args.chunk, max_queue=args.max_queue, **srv_mode)
     else:
         srv = TutoringServer(eng, args.port, args.host, args.max_batch, args.window_ms, args.max_length,
                              args.repetition_penalty, tokenizer=tok, batching=args.batching, chunk=args.chunk,
-                             max_queue=args.max_queue, **mode)
+                             max_queue=args.max_queue, **srv_mode)
     done = threading.Event()
     fatal: list = []
 
@@ -783,6 +886,9 @@ def main(argv=None):
         log.info("prompt-prefix cache: %d of %d admitted prompts shared the prefix (%.1f %%), %d prefill rows skipped",
                  eng.prefix_hits, eng.prefix_prompts, 100.0 * eng.prefix_hits / eng.prefix_prompts,
                  eng.prefix_rows_skipped)
+    if isinstance(getattr(srv, "front", None), LogprobMeter):
+        log.info("log-probabilities: %s over %d answered queries",
+                 ", ".join(f"{k} {v}" for k, v in logprob_stats(srv.front).items()), srv.front.answers)
     if proxy is not None:
         proxy.close()  # releases the followers, which close their engines (below, same order)
         eng = proxy.engine

@@ -1,0 +1,458 @@
+"""Log-probabilities on the GPU: the token_logprob kernel (ops/csrc/logprob.hip) against the Python
+definition (models/gpt2.py reference_logprob) in both of its modes, then the engine through every
+decode path, graphs and eager, held to the fp32 oracle's teacher-forced log-probabilities; with
+sampling, controls, the fp8 cache, the prefix cache and continuous batching; score(); unsupported
+combinations."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import logprob_cases as lc
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+PEN = lc.PEN
+T_MAX = lc.KERNEL_MAX_LEN
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+# ------------------------------------------------------------------ the kernel
+def _reference(z, seen, tok, vocab, penalty):
+    from distributed_lms_raft_llm_amd.models.gpt2 import reference_logprob
+
+    return np.array([reference_logprob(z[i, :vocab], None if seen is None else seen[i, :vocab], penalty, tok[i])
+                     for i in range(z.shape[0])])
+
+
+def _decode_state(n, mapped, dead=()):
+    """Slots of ``n`` rows: row i lives in slot i, or (mapped) in slot perm[i] of n + 3; lengths
+    0 .. T_MAX - 1 in turn; the rows of ``dead`` alternately finished and at max_length."""
+    S = n + 3 if mapped else n
+    slot_of = [(5 * i + 2) % S for i in range(n)] if mapped else list(range(n))
+    assert len(set(slot_of)) == n
+    lens = np.full(S, 3, dtype=np.int32)
+    fin = np.zeros(S, dtype=np.int32)
+    for i in range(n):
+        lens[slot_of[i]] = (i * 5) % T_MAX
+    for k, i in enumerate(dead):
+        if k % 2:
+            fin[slot_of[i]] = 1
+        else:
+            lens[slot_of[i]] = T_MAX
+    if mapped:  # the slots no row maps to look live: they must stay untouched all the same
+        for s in set(range(S)) - set(slot_of):
+            lens[s], fin[s] = 1, 0
+    return S, slot_of, lens, fin
+
+
+@pytest.mark.parametrize("mapped", [False, True])
+@pytest.mark.parametrize("rows", lc.KERNEL_ROWS)
+@pytest.mark.parametrize("vocab,ld", lc.KERNEL_SHAPES)
+def test_token_logprob_decode_mode(vocab, ld, rows, mapped):
+    from distributed_lms_raft_llm_amd import ops
+    from distributed_lms_raft_llm_amd.models.gpt2 import penalised_logits_f32
+
+    worst = 0.0
+    for penalty, pad in ((1.0, 1e30), (1.2, float("nan"))):
+        z, seen, tok = lc.kernel_rows(rows, vocab, ld, seed=vocab + rows, pad=pad)
+        n = z.shape[0]
+        want = _reference(z, seen, tok, vocab, penalty)
+        assert np.all(np.isfinite(want)) and np.all(want <= 0)
+        assert np.abs(want[2 * rows: 3 * rows]).max() < 1e-6  # one logit 40 above the rest
+        if penalty == 1.0:
+            assert np.abs(want[3 * rows: 4 * rows] + math.log(vocab)).max() < 1e-9  # the constant row
+        l_tok = np.array([penalised_logits_f32(z[i, :vocab], seen[i, :vocab], penalty)[tok[i]] for i in range(n)])
+        keys = np.zeros((n, 2), dtype=np.int64)
+        keys[:, 0], keys[:, 1] = lc.sampler_keys(l_tok, tok), -1  # (the second column is never read)
+        zd, sd, kd = _t(z), _t(lc.pack_seen(seen)), _t(keys)
+        for dead in ((), (1, 2, n - 1)):
+            S, slot_of, lens, fin = _decode_state(n, mapped, dead)
+            out = torch.full((S, T_MAX), lc.SENTINEL, dtype=torch.float32, device=DEV)
+            smap = _t(np.asarray(slot_of, dtype=np.int32)) if mapped else None
+            ops.token_logprob(zd[:, :vocab], vocab, out, keys=kd, seen=sd, lens=_t(lens), finished=_t(fin),
+                              penalty=penalty, slot_map=smap)
+            got = out.cpu().numpy()
+            expect = np.full((S, T_MAX), lc.SENTINEL, dtype=np.float64)
+            for i in range(n):
+                if i not in dead:
+                    expect[slot_of[i], lens[slot_of[i]]] = want[i]
+            # the value at [slot][lens[slot]] and nowhere else; finished slots and slots at max_length untouched
+            assert np.array_equal(got == lc.SENTINEL, expect == lc.SENTINEL), (penalty, dead)
+            live = expect != lc.SENTINEL
+            assert live.sum() == n - len(dead)
+            err = np.abs(got[live] - expect[live]).max()
+            worst = max(worst, err)
+            assert err <= lc.KERNEL_TOL, (penalty, dead, err)
+    print(f"token_logprob decode vocab {vocab} rows {rows} mapped {mapped}: largest error {worst:.3g}")
+
+
+@pytest.mark.parametrize("rows", lc.KERNEL_ROWS)
+@pytest.mark.parametrize("vocab,ld", lc.KERNEL_SHAPES)
+def test_token_logprob_teacher_forced_mode(vocab, ld, rows):
+    from distributed_lms_raft_llm_amd import ops
+
+    for pad in (1e30, float("nan")):
+        z, _, tok = lc.kernel_rows(rows, vocab, ld, seed=vocab + rows, pad=pad)
+        n = z.shape[0]
+        want = _reference(z, None, tok, vocab, 1.0)
+        assert np.abs(want[3 * rows: 4 * rows] + math.log(vocab)).max() < 1e-9
+        out = torch.full((n + 4,), lc.SENTINEL, dtype=torch.float32, device=DEV)
+        ops.token_logprob(_t(z)[:, :vocab], vocab, out[:n], targets=_t(tok.astype(np.int32)))
+        got = out.cpu().numpy()
+        assert np.all(got[n:] == lc.SENTINEL)
+        err = np.abs(got[:n] - want).max()
+        print(f"token_logprob teacher-forced vocab {vocab} rows {rows}: largest error {err:.3g}")
+        assert err <= lc.KERNEL_TOL
+    # a target outside the vocabulary indexes nothing: the row's value is NaN, its neighbours' are right
+    bad = tok.astype(np.int32).copy()
+    bad[0] = vocab
+    ops.token_logprob(_t(z)[:, :vocab], vocab, out[:n], targets=_t(bad))
+    got = out.cpu().numpy()
+    assert math.isnan(got[0]) and np.abs(got[1:n] - want[1:]).max() <= lc.KERNEL_TOL
+
+
+def test_token_logprob_refuses_bad_arguments():
+    from distributed_lms_raft_llm_amd import ops
+
+    n, vocab, ld = 2, 1000, 1024
+    z = torch.zeros(n, ld, device=DEV)
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=DEV)  # noqa: E731
+    keys = torch.zeros(n, 1, dtype=torch.int64, device=DEV)
+    seen, out, out1 = i32(n, ld // 32), torch.zeros(n, T_MAX, device=DEV), torch.zeros(n, device=DEV)
+    good = dict(keys=keys, seen=seen, lens=i32(n), finished=i32(n), penalty=PEN)
+    ops.token_logprob(z[:, :vocab], vocab, out, **good)
+    ops.token_logprob(z[:, :vocab], vocab, out1, targets=i32(n))
+    for bad in (lambda: ops.token_logprob(z[:, :vocab], vocab + 1, out, **good),
+                lambda: ops.token_logprob(z[:, 1:vocab + 1], vocab, out, **good),  # misaligned rows
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out, **dict(good, penalty=0.0)),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out, **dict(good, lens=i32(1))),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out, **dict(good, seen=i32(n, 8))),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out[:1], **good),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out, **dict(good, slot_map=i32(1))),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out, **dict(good, keys=None)),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out1, targets=i32(1)),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out1, targets=i32(n), penalty=PEN),
+                lambda: ops.token_logprob(z[:, :vocab], vocab, out1, targets=i32(n), seen=seen)):
+        with pytest.raises(ValueError):
+            bad()
+    with pytest.raises(TypeError):
+        ops.token_logprob(z.half()[:, :vocab], vocab, out, **good)
+    # the host entry point itself refuses what the binding would have caught: hipErrorInvalidValue (1)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def entry(logits=P(z), ldz=ld, seen_p=P(seen), words=ld // 32, keys_p=P(keys), ldk=1, targets=None,
+              lens=P(good["lens"]), fin=P(good["finished"]), smap=None, nslots=n, penalty=PEN, v=vocab, tmax=T_MAX,
+              out_p=P(out), ldo=T_MAX, B=n):
+        return ops.lib().dlms_token_logprob(logits, ldz, seen_p, words, keys_p, ldk, targets, lens, fin, smap, nslots,
+                                            penalty, v, tmax, out_p, ldo, B, st)
+
+    assert entry() == 0
+    big = torch.zeros(1, 65540, device=DEV)
+    for kw in (dict(ldz=ld + 2), dict(logits=P(big), ldz=65540, v=65537, words=2049),
+               dict(logits=ctypes.c_void_p(z.data_ptr() + 4)), dict(penalty=0.0), dict(penalty=-1.0), dict(v=0),
+               dict(ldz=vocab - 4), dict(words=vocab // 32), dict(ldo=T_MAX - 1), dict(tmax=0), dict(B=0),
+               dict(ldk=0), dict(keys_p=None), dict(lens=None), dict(targets=P(i32(n)))):  # (targets with decode state)
+        assert entry(**kw) == 1, kw
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------ engine
+@pytest.fixture(scope="module")
+def model():
+    from distributed_lms_raft_llm_amd.models.config import gpt2_config
+    from distributed_lms_raft_llm_amd.models.gpt2 import GPT2Reference
+
+    cfg = gpt2_config("gpt2")
+    w = lc.bf16_exact_weights(cfg)
+    return cfg, w, GPT2Reference(cfg, w, device="cuda")
+
+
+def _make(cfg, w, kind):
+    """The engines of tests/test_controls_gpu.py."""
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine
+
+    if kind == "small":  # 1 row, 2 rows (latency path), 9 rows (mid path)
+        return HipGPT2Engine(cfg, w, max_batch=16, max_length=40)
+    if kind == "panel":  # 256 rows: the panel-resident LM head
+        return HipGPT2Engine(cfg, w, max_batch=256, max_length=24)
+    eng = HipGPT2Engine(cfg, w, max_batch=16, max_length=40, overlap=True, overlap_min_batch=2, overlap_parts=2)
+    eng.mid_max = 0
+    return eng
+
+
+@pytest.fixture(scope="module")
+def engines(model):
+    cfg, w, _ = model
+    made = {}
+
+    def get(kind):
+        if kind not in made:
+            made[kind] = _make(cfg, w, kind)
+        return made[kind]
+
+    yield get
+    for e in made.values():
+        e.close()
+
+
+def _check_tokens(oracle, outs, prompts, eps=0.05):
+    """(a) no mismatch at a decisive position of the fp32 oracle."""
+    from distributed_lms_raft_llm_amd.models.gpt2 import teacher_forced_check_batch
+
+    rs = teacher_forced_check_batch(oracle, outs, [len(p) for p in prompts], PEN, eps=eps)
+    for r, o, p in zip(rs, outs, prompts):
+        assert o[: len(p)] == p and r["positions"] == len(o) - len(p) and not r["mismatches"], r["mismatches"]
+
+
+def _check_logprobs(oracle, outs, lps, prompts, eps, what, controls=None):
+    """(b) finite, one per generated token, within ``eps`` of the oracle's teacher-forced
+    log-probabilities of the engine's own sequence.  Returns the largest difference."""
+    from distributed_lms_raft_llm_amd.models.gpt2 import teacher_forced_logprobs
+
+    worst, lo, hi = 0.0, 0.0, -1e9
+    assert len(lps) == len(outs) == len(prompts)
+    for o, lp, p in zip(outs, lps, prompts):
+        assert len(lp) == len(o) - len(p) > 0 and all(isinstance(v, float) and math.isfinite(v) for v in lp), lp
+        want = teacher_forced_logprobs(oracle, o, len(p), PEN, controls)
+        worst = max(worst, float(np.abs(np.asarray(lp) - want).max()))
+        lo, hi = min(lo, min(lp)), max(hi, max(lp))
+    print(f"logprobs {what}: largest |engine - oracle| {worst:.5f} (tolerance {eps:.5f}), values {lo:.2f} .. {hi:.2f}")
+    assert worst <= eps, (what, worst, eps)
+    return worst
+
+
+@pytest.mark.parametrize("kind,n", lc.ENGINE_CASES)
+def test_engine_logprobs(model, engines, kind, n):
+    cfg, _, oracle = model
+    eng = engines(kind)
+    T = eng.max_length
+    prompts = lc.prompts(cfg, n)
+    if kind == "panel":
+        assert eng.ps_lm and n >= eng.PS_LM_MIN_ROWS
+    if kind == "overlap":
+        assert eng._overlap_ok(16) and not eng._small_ok(16)
+    res = {}
+    for graph in (True, False):
+        eng.use_graph = graph
+        greedy = eng.generate(prompts, repetition_penalty=PEN)
+        toks, lps = eng.generate(prompts, repetition_penalty=PEN, logprobs=True)
+        assert all(len(p) < len(o) <= T for o, p in zip(toks, prompts))
+        if graph:  # (a), (b): the eager run is held to be these sequences and values below
+            _check_tokens(oracle, toks, prompts)
+            _check_logprobs(oracle, toks, lps, prompts, lc.LOGPROB_EPS, f"{kind} {n} rows")
+        # (c) a repeated call returns the same, bit for bit
+        assert eng.generate(prompts, repetition_penalty=PEN, logprobs=True) == (toks, lps)
+        # (d) a plain greedy call afterwards returns what it returned before and allocates nothing
+        held = (eng._logits, eng.out_logprob, eng.prompt_len)
+        ptrs = [t.data_ptr() for t in held]
+        graphs = set(eng._graphs)
+        assert eng.generate(prompts, repetition_penalty=PEN) == greedy
+        assert all(a is b for a, b in zip((eng._logits, eng.out_logprob, eng.prompt_len), held))
+        assert [t.data_ptr() for t in held] == ptrs and set(eng._graphs) == graphs
+        assert not eng._logprobs and eng._lp_rows is None
+        res[graph] = (toks, lps)
+    eng.use_graph = True
+    assert res[True][0] == res[False][0], "graph replay and eager disagree on the tokens"
+    assert res[True][1] == res[False][1], "graph replay and eager disagree on the log-probabilities"
+
+
+def test_logprobs_bypass_the_dataflow_decode(model, engines, monkeypatch):
+    """(e) one row: greedy decodes on the persistent dataflow kernel (where the engine has it), a call
+    with logprobs never launches it."""
+    cfg, _, _ = model
+    eng = engines("small")
+    eng.use_graph = True
+    launches = []
+    run = eng._df_run
+    monkeypatch.setattr(eng, "_df_run", lambda *a: launches.append(a) or run(*a))
+    prompts = lc.prompts(cfg, 1)
+    with eng._logprobs_scope(True):
+        assert not eng._df_ok(1)
+    eng.generate(prompts, repetition_penalty=PEN, logprobs=True)
+    eng.decode(1, 2, PEN, logprobs=True)
+    assert not launches
+    eng.generate(prompts, repetition_penalty=PEN)
+    assert bool(launches) == bool(eng.dataflow)
+
+
+def test_engine_logprobs_with_sampling(model, engines):
+    from distributed_lms_raft_llm_amd.models.config import SamplingParams
+    from distributed_lms_raft_llm_amd.models.gpt2 import teacher_forced_sampling_check
+
+    cfg, _, oracle = model
+    eng = engines("small")
+    eng.use_graph = True
+    prompts = lc.prompts(cfg, 9)
+    sp = SamplingParams(0.7, 50, 0.9, 7)
+    plain = eng.generate(prompts, repetition_penalty=PEN, sampling=sp)
+    toks, lps = eng.generate(prompts, repetition_penalty=PEN, sampling=sp, logprobs=True)
+    assert toks == plain  # the same logits, the same draws
+    for o, p in zip(toks, prompts):
+        r = teacher_forced_sampling_check(oracle, o, len(p), PEN, sp)
+        assert r["positions"] == len(o) - len(p) and not r["mismatches"], r["mismatches"]
+    # temperature 1, ahead of top-k / top-p: the oracle's log-probabilities know nothing of sp
+    _check_logprobs(oracle, toks, lps, prompts, lc.LOGPROB_EPS, "sampling 9 rows")
+    eng.use_graph = False
+    assert eng.generate(prompts, repetition_penalty=PEN, sampling=sp, logprobs=True) == (toks, lps)
+    eng.use_graph = True
+
+
+def test_engine_logprobs_with_controls(model, engines):
+    from distributed_lms_raft_llm_amd.models.config import GenerationControls
+    from distributed_lms_raft_llm_amd.models.gpt2 import teacher_forced_controls_check_batch
+
+    cfg, _, oracle = model
+    eng = engines("small")
+    eng.use_graph = True
+    prompts = lc.prompts(cfg, 9)
+    ct = GenerationControls(no_repeat_ngram_size=2)
+    plain = eng.generate(prompts, repetition_penalty=PEN, controls=ct)
+    toks, lps = eng.generate(prompts, repetition_penalty=PEN, controls=ct, logprobs=True)
+    assert toks == plain
+    for r in teacher_forced_controls_check_batch(oracle, toks, [len(p) for p in prompts], PEN, ct):
+        assert not r["mismatches"], r["mismatches"]
+    _check_logprobs(oracle, toks, lps, prompts, lc.LOGPROB_EPS, "no_repeat_ngram_size=2, 9 rows", controls=ct)
+
+
+def test_engine_logprobs_on_the_fp8_cache(model):
+    import kv_fp8_cases as kc
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine
+    from distributed_lms_raft_llm_amd.models.gpt2 import GPT2Reference
+
+    cfg, w, _ = model
+    prompts = lc.prompts(cfg, lc.NOISE_ROWS)
+    eng = HipGPT2Engine(cfg, w, max_batch=16, max_length=lc.NOISE_T, kv_dtype="fp8")
+    try:
+        toks, lps = eng.generate(prompts, repetition_penalty=PEN, logprobs=True)
+        assert eng.generate(prompts, repetition_penalty=PEN, logprobs=True) == (toks, lps)
+    finally:
+        eng.close()
+    oracle8 = GPT2Reference(cfg, w, device="cuda", kv_dtype="fp8")
+    _check_tokens(oracle8, toks, prompts, eps=kc.KV_FP8_EPS["gpt2"])
+    _check_logprobs(oracle8, toks, lps, prompts, lc.LOGPROB_EPS_FP8, "fp8 cache 9 rows")
+
+
+def test_engine_logprobs_with_the_prefix_cache(model):
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine
+
+    cfg, w, oracle = model
+    prefix = lc.prompts(cfg, 1, seed=9)[0] + [17, 4242, 17, 4242, 17]
+    prompts = [prefix + s for s in lc.prompts(cfg, 4)]
+    eng = HipGPT2Engine(cfg, w, max_batch=4, max_length=40, prefix_capacity=64)
+    try:
+        eng.set_prompt_prefix(prefix)
+        toks, lps = eng.generate(prompts, repetition_penalty=PEN, logprobs=True)
+        assert eng.prefix_hits == 4
+        assert eng.generate(prompts, repetition_penalty=PEN, logprobs=True) == (toks, lps)
+    finally:
+        eng.close()
+    _check_tokens(oracle, toks, prompts)
+    _check_logprobs(oracle, toks, lps, prompts, lc.LOGPROB_EPS, "prefix cache 4 rows")
+
+
+def test_continuous_batching_with_logprobs(model):
+    """Chunk 4, four slots, seven requests through ContinuousBatcher(logprobs=True): the later ones are
+    admitted into slots freed mid-run; every result is held to the oracle serving it alone."""
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine
+    from distributed_lms_raft_llm_amd.engine.scheduler import ContinuousBatcher
+
+    cfg, w, oracle = model
+    prompts = lc.prompts(cfg, 7)
+    eng = HipGPT2Engine(cfg, w, max_batch=4, max_length=40, prefill_split=1)
+    try:
+        cb = ContinuousBatcher(eng, PEN, chunk=4, logprobs=True)
+        try:
+            outs = [f.result(120) for f in [cb.submit(p) for p in prompts]]
+        finally:
+            cb.stop()
+    finally:
+        eng.close()
+    toks, lps = [o[0] for o in outs], [o[1] for o in outs]
+    _check_tokens(oracle, toks, prompts)
+    _check_logprobs(oracle, toks, lps, prompts, lc.LOGPROB_EPS, "continuous batching 7 requests")
+
+
+def _raw_logprobs(oracle, seq):
+    """The fp32 reference's raw log_softmax of tokens 1 .. len - 1 of ``seq`` (float64)."""
+    from distributed_lms_raft_llm_amd.models.gpt2 import KVCache
+
+    S = len(seq)
+    dev = oracle.device
+    cache = KVCache.allocate(oracle.cfg, 1, S, dtype=oracle.dtype, device=dev)
+    hidden = oracle.forward(torch.tensor([seq], device=dev), torch.arange(S, device=dev)[None], cache,
+                            torch.zeros(1, dtype=torch.long, device=dev))[0]
+    lsm = torch.log_softmax(oracle.logits(hidden[: S - 1]).double(), dim=-1)
+    return lsm[torch.arange(S - 1, device=dev), torch.tensor(seq[1:], device=dev)].cpu().numpy()
+
+
+def test_score(model, engines):
+    cfg, _, oracle = model
+    eng = engines("small")
+    eng.use_graph = True
+    assert eng.max_batch == 16
+    full = eng.generate(lc.prompts(cfg, 5), repetition_penalty=PEN)
+    assert all(len(o) == 40 for o in full[:2])
+    ragged = [full[0][:40], full[1][:33], full[2][:19], full[3][:7], full[4][:2]]
+    with torch.no_grad():
+        for seqs in ([full[0][:2]], ragged, [[full[0][0]]], ragged[2:4] + [[5]]):
+            got = eng.score(seqs)
+            assert [len(g) for g in got] == [len(s) - 1 for s in seqs]
+            worst = 0.0
+            for s, g in zip(seqs, got):
+                if len(s) > 1:
+                    assert all(isinstance(v, float) and math.isfinite(v) and v < 0 for v in g)
+                    worst = max(worst, float(np.abs(np.asarray(g) - _raw_logprobs(oracle, s)).max()))
+            print(f"score {[len(s) for s in seqs]}: largest |engine - oracle| {worst:.5f} "
+                  f"(tolerance {lc.LOGPROB_EPS:.5f})")
+            assert worst <= lc.LOGPROB_EPS
+            assert eng.score(seqs) == got
+    assert sum(len(s) - 1 for s in ragged) > 3 * eng.max_batch  # several LM-head chunks
+    assert eng.score([]) == []
+    for bad in ([[]], [[1, 2]] * 17, [list(range(41))], [[cfg.vocab_size]]):
+        with pytest.raises(ValueError):
+            eng.score(bad)
+    # an unfinished slot: refused, like set_prompt_prefix
+    greedy = eng.generate(lc.prompts(cfg, 2), repetition_penalty=PEN)
+    eng.admit(lc.prompts(cfg, 1), [0], PEN)
+    with pytest.raises(RuntimeError, match="unfinished"):
+        eng.score(ragged)
+    eng.decode(1, 39, PEN)
+    assert eng.finished_flags(1) == [1]
+    assert len(eng.score(ragged[3:])[0]) == 6
+    assert eng.generate(lc.prompts(cfg, 2), repetition_penalty=PEN) == greedy
+
+
+def test_unsupported_combinations_raise(model, engines):
+    from distributed_lms_raft_llm_amd.engine.gpt2_engine import HipGPT2Engine, logprobs_unsupported
+
+    cfg, w, _ = model
+    e8 = HipGPT2Engine(cfg, w, max_batch=2, max_length=24, weight_dtype="fp8")
+    try:
+        for call in (lambda: e8.generate([[1, 2]], logprobs=True), lambda: e8.admit([[1, 2]], [0], logprobs=True),
+                     lambda: e8.decode(2, 1, logprobs=True), lambda: e8.warm_decode_graphs(logprobs=True),
+                     lambda: e8.score([[1, 2]])):
+            with pytest.raises(ValueError, match="fp8"):
+                call()
+        assert len(e8.generate([[1, 2]])[0]) > 2 and e8.out_logprob is None  # greedy still serves
+        with pytest.raises(ValueError):
+            e8.collect([0], logprobs=True)
+    finally:
+        e8.close()
+    eng = engines("small")
+    eng.tp_size = 2  # (what a TP rank's engine reports; the check runs before any device work)
+    try:
+        with pytest.raises(ValueError, match="tensor parallelism"):
+            eng.generate([[1, 2]], logprobs=True)
+        with pytest.raises(ValueError, match="tensor parallelism"):
+            eng.score([[1, 2]])
+    finally:
+        eng.tp_size = 1
+    assert len(eng.generate([[1, 2]])[0]) > 2
+    assert "tensor parallelism" in logprobs_unsupported(8, False) and logprobs_unsupported(1, False) is None
