@@ -36,6 +36,8 @@ import torch
 from .. import ops
 from ..models.config import GenerationControls, GPT2Config, SamplingParams
 from ..utils.metrics import METRICS
+from .mode import (DecodeMode, controls_unsupported, kv_fp8_unsupported, logprobs_unsupported,  # noqa: F401
+                   prefix_unsupported, sampling_unsupported)
 from .weights import GPT2DeviceWeights, prepare_gpt2_weights
 
 log = logging.getLogger(__name__)
@@ -169,65 +171,6 @@ def _bucket(n: int) -> int:
         if n <= b:
             return b
     return (n + 255) // 256 * 256
-
-
-# greedy decoding through the sampler (banning GenerationControls): its definition at top_k = 1
-_GREEDY_AS_SAMPLING = SamplingParams(1.0, 1, 1.0, 0)
-
-
-def sampling_unsupported(tp_size: int, fp8: bool) -> str | None:
-    """Why an engine of this shape cannot sample (None: it can)."""
-    if tp_size > 1:
-        return ("sampling is not supported with tensor parallelism (tp_size > 1): the device sampler ranks one "
-                "rank's whole vocabulary; serve greedy or TP=1")
-    if fp8:
-        return ("sampling is not supported with fp8 weights: the fp8 LM head has no f32-logits epilogue; serve "
-                "greedy or weight_dtype='bf16'")
-    return None
-
-
-def kv_fp8_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
-    """Why an engine of this shape cannot hold an fp8 (e4m3) KV cache (None: it can)."""
-    if tp_size > 1:
-        return ("the fp8 KV cache is not supported with tensor parallelism (tp_size > 1): the TP-fused decode path "
-                "has no fp8-cache build; serve kv_dtype='bf16' or TP=1")
-    if fp8_weights:
-        return ("the fp8 KV cache is not supported with fp8 weights: the W8A8 QKV GEMM has no fp8-cache epilogue; "
-                "serve kv_dtype='bf16' or weight_dtype='bf16'")
-    return None
-
-
-def prefix_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
-    """Why an engine of this shape cannot keep a prompt-prefix cache (None: it can)."""
-    if tp_size > 1:
-        return ("the prompt-prefix cache is not supported with tensor parallelism (tp_size > 1): the prefix store "
-                "and its fill are built for one rank's whole cache; serve prefix_capacity=0 or TP=1")
-    if fp8_weights:
-        return ("the prompt-prefix cache is not supported with fp8 weights: the suffix-only prefill is verified on "
-                "the bf16 GEMMs only; serve prefix_capacity=0 or weight_dtype='bf16'")
-    return None
-
-
-def controls_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
-    """Why an engine of this shape cannot serve ``GenerationControls`` (None: it can)."""
-    if tp_size > 1:
-        return ("generation controls are not supported with tensor parallelism (tp_size > 1): the device bans "
-                "work on one rank's whole vocabulary; serve without controls or TP=1")
-    if fp8_weights:
-        return ("generation controls are not supported with fp8 weights: the fp8 LM head has no f32-logits "
-                "epilogue for the bans; serve without controls or weight_dtype='bf16'")
-    return None
-
-
-def logprobs_unsupported(tp_size: int, fp8_weights: bool) -> str | None:
-    """Why an engine of this shape cannot return log-probabilities (None: it can)."""
-    if tp_size > 1:
-        return ("log-probabilities are not supported with tensor parallelism (tp_size > 1): the device log-softmax "
-                "reduces one rank's whole vocabulary; serve without logprobs or TP=1")
-    if fp8_weights:
-        return ("log-probabilities are not supported with fp8 weights: the fp8 LM head has no f32-logits epilogue "
-                "to take them from; serve without logprobs or weight_dtype='bf16'")
-    return None
 
 
 def split_prefix(prompts, prefix) -> list[int]:
@@ -580,23 +523,17 @@ class HipGPT2Engine:
         self._side_streams: list[torch.cuda.Stream] = []
         self._flags: torch.Tensor | None = None
         self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
-        # sampling (None: greedy): the parameters of the public call in progress (_sampling_scope);
-        # the f32 logits scratch of the sampled LM head, allocated on the first sampled call
-        self._sampling: SamplingParams | None = None
+        # the generation mode of the public call in progress (_mode_scope; the default: greedy), and
+        # what the modes need, allocated on the first call that needs it (_alloc_for): the f32 logits
+        # scratch of the sampled LM head, every slot's prompt length, the device tables of the stop
+        # sequences seen, the chosen tokens' log-probabilities [slot][position]
+        self._mode = DecodeMode()
         self._logits: torch.Tensor | None = None
-        self._rng_seed_host: int | None = None  # the seed in rng_seed (None: never set)
-        self._rng_count = 0  # requests admitted since the seed was last set: the next stream id
-        # generation controls (None: none) of the public call in progress (_controls_scope); every
-        # slot's prompt length and the device tables of the stop sequences seen, allocated on the
-        # first call with controls
-        self._controls: GenerationControls | None = None
         self.prompt_len: torch.Tensor | None = None
         self._stop_tables: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}
-        # log-probabilities (False: none) of the public call in progress (_logprobs_scope); the
-        # chosen tokens' log-probabilities [slot][position], allocated on the first such call
-        self._logprobs = False
         self.out_logprob: torch.Tensor | None = None
-        self._lp_rows: list | None = None  # generate(logprobs=True): the rows' results while it runs
+        self._rng_seed_host: int | None = None  # the seed in rng_seed (None: never set)
+        self._rng_count = 0  # requests admitted since the seed was last set: the next stream id
         self._alloc_state()
         self.xgmi = None
         if self.tp_size > 1:
@@ -881,176 +818,103 @@ class HipGPT2Engine:
                             hscale: torch.Tensor | None = None, slot_map: torch.Tensor | None = None, lo: int = 0,
                             ln1_out: torch.Tensor | None = None):
         """LM head with the fused penalty + argmax on ``hidden`` (bf16, or e4m3 with ``hscale``) --
-        inside a ``_sampling_scope``: f32 logits and the device sampler instead -- then the
-        bookkeeping of the chosen token.  Rows map to slots [lo, lo + B) or through ``slot_map``.
-        ``ln1_out`` (rows [lo, lo + B)): the update also writes layer 0's LN1 of the new rows there."""
-        cfg = self.cfg
+        in a mode with a ``sampler``: f32 logits, the bans, the device sampler and the chosen token's
+        log-probability instead -- then the bookkeeping of the chosen token.  Rows map to slots
+        [lo, lo + B) or through ``slot_map``.  ``ln1_out`` (rows [lo, lo + B), never with a slot
+        map): the update also writes layer 0's LN1 of the new rows there."""
+        cfg, mode = self.cfg, self._mode
         hi = lo + B
+
+        def rows(t):  # per-slot state as the kernels take it: the rows' slots, or all of them under a slot map
+            return t[lo:hi] if slot_map is None else t
+
         seen_rows = self.seen[lo:hi] if seen is None else seen
+        kp = self.key_parts[lo:hi]
         P = self.key_parts.shape[1]  # partial keys per row the LM head writes (and the consumer reads)
-        sp, ct = self._sampling, self._controls
-        if sp is None and ((ct is not None and ct.bans) or self._logprobs):
-            sp = _GREEDY_AS_SAMPLING  # the sampler's definition at top_k = 1: the largest unbanned key
+        sp = mode.sampler
         if sp is not None:
-            # sampling: raw f32 logits (the GEMMs' plain f32 epilogues; the penalty moves into the
-            # sampler), then one drawn key per row in the first key column
-            if self._sampling is not None:
-                self._check_sampling(sp)
+            # raw f32 logits (the GEMMs' plain f32 epilogues; the penalty moves into the sampler),
+            # then one drawn key per row in the first key column
             if hidden.dtype == ops.FP8 or self._logits is None:
-                raise ValueError("sampled LM head: bf16 hidden rows inside a _sampling_scope / _controls_scope / "
-                                 "_logprobs_scope")
+                raise ValueError("sampled LM head: bf16 hidden rows inside a _mode_scope")
             z = self._logits[lo:hi]
             if self.ps_lm and B >= self.PS_LM_MIN_ROWS:
                 ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
             else:
                 ops.gemm(hidden, self.w.lm_head, ops.EPI_F32, out=z)
             P = 1
-            if ct is not None and ct.bans:
-                # controls: -inf at the banned tokens of every live row, between the logits and the sampler
-                if slot_map is None:
-                    ops.logit_bans(z, self.lens[lo:hi], self.finished[lo:hi], self.prompt_len[lo:hi],
-                                   self.out_tokens[lo:hi], ct.no_repeat_ngram_size, ct.min_new_tokens,
-                                   cfg.eos_token_id, cfg.vocab_size)
-                else:
-                    ops.logit_bans(z, self.lens, self.finished, self.prompt_len, self.out_tokens,
-                                   ct.no_repeat_ngram_size, ct.min_new_tokens, cfg.eos_token_id, cfg.vocab_size,
-                                   slot_map=slot_map)
-            if slot_map is None:
-                ops.sample_topk_topp(z, seen_rows, self.lens[lo:hi], self.rng_stream[lo:hi], self.rng_seed, penalty,
-                                     sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi])
-            else:
-                ops.sample_topk_topp(z, seen_rows, self.lens, self.rng_stream, self.rng_seed, penalty,
-                                     sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, self.key_parts[lo:hi],
-                                     slot_map=slot_map)
-            if self._logprobs:
+            if mode.bans:
+                # -inf at the banned tokens of every live row, between the logits and the sampler
+                ops.logit_bans(z, rows(self.lens), rows(self.finished), rows(self.prompt_len), rows(self.out_tokens),
+                               mode.bans.no_repeat_ngram_size, mode.bans.min_new_tokens, cfg.eos_token_id,
+                               cfg.vocab_size, slot_map=slot_map)
+            ops.sample_topk_topp(z, seen_rows, rows(self.lens), rows(self.rng_stream), self.rng_seed, penalty,
+                                 sp.temperature, sp.top_k, sp.top_p, cfg.vocab_size, kp, slot_map=slot_map)
+            if mode.logprobs:
                 # the chosen token's log-probability into out_logprob[slot][lens[slot]]: behind the
                 # sampler, which chose it, and ahead of the update, which advances lens
-                if slot_map is None:
-                    ops.token_logprob(z, cfg.vocab_size, self.out_logprob[lo:hi], keys=self.key_parts[lo:hi],
-                                      seen=seen_rows, lens=self.lens[lo:hi], finished=self.finished[lo:hi],
-                                      penalty=penalty)
-                else:
-                    ops.token_logprob(z, cfg.vocab_size, self.out_logprob, keys=self.key_parts[lo:hi], seen=seen_rows,
-                                      lens=self.lens, finished=self.finished, penalty=penalty, slot_map=slot_map)
+                ops.token_logprob(z, cfg.vocab_size, rows(self.out_logprob), keys=kp, seen=seen_rows,
+                                  lens=rows(self.lens), finished=rows(self.finished), penalty=penalty,
+                                  slot_map=slot_map)
         elif hidden.dtype != ops.FP8 and self.ps_lm and B >= self.PS_LM_MIN_ROWS:
             P = ops.gemm_ps_key_slots(B, self.lm_head_sh.shape[0] * 16, self.lm_head_sh.shape[1] * 32)
-            ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_ARGMAX, argmax_out=self.key_parts[lo:hi], seen=seen_rows,
+            ops.gemm_ps(hidden, self.lm_head_sh, ops.EPI_ARGMAX, argmax_out=kp, seen=seen_rows,
                         vocab=cfg.vocab_size, col_offset=self.w.vocab_range[0], penalty=penalty)
         elif hidden.dtype == ops.FP8:
-            ops.gemm(hidden, self.w.lm_head8, ops.EPI_ARGMAX, argmax_out=self.key_parts[lo:hi], seen=seen_rows,
+            ops.gemm(hidden, self.w.lm_head8, ops.EPI_ARGMAX, argmax_out=kp, seen=seen_rows,
                      vocab=cfg.vocab_size, col_offset=self.w.vocab_range[0], penalty=penalty, a_scale=hscale,
                      w_scale=self.w.s_lm)
         else:
-            ops.gemm(hidden, self.w.lm_head, ops.EPI_ARGMAX, argmax_out=self.key_parts[lo:hi], seen=seen_rows,
+            ops.gemm(hidden, self.w.lm_head, ops.EPI_ARGMAX, argmax_out=kp, seen=seen_rows,
                      vocab=cfg.vocab_size, col_offset=self.w.vocab_range[0], penalty=penalty)
         if lo:
             if self.tp_size > 1:
                 raise ValueError("row-offset LM head is TP=1 only")
-            keys = self.key_parts[lo:hi, :P]
+            keys = kp[:, :P]
         else:
             keys = self._gather_keys(B, P)
-        if ct is not None and ct.stop:
-            # controls with stop sequences: the same update, which also finishes a row at a match
-            sl, stk = self._stop_tables[ct.stop]
-            l0 = self.w.layers[0]
-            if slot_map is None:
-                ops.decode_update_stop(keys, self.lens[lo:hi], self.finished[lo:hi], self.out_tokens[lo:hi],
-                                       self.seen[lo:hi], self.cur_tok[lo:hi], self.cur_pos[lo:hi],
-                                       self.cur_kvlen[lo:hi], self.w.wte, self.w.wpe, self.x[lo:hi], cfg.eos_token_id,
-                                       self.max_length, self.prompt_len[lo:hi], sl, stk,
-                                       ln=(l0.ln1_g, l0.ln1_b, cfg.layer_norm_epsilon) if ln1_out is not None else None,
-                                       h=ln1_out)
-            else:
-                ops.decode_update_stop(keys, self.lens, self.finished, self.out_tokens, self.seen, self.cur_tok,
-                                       self.cur_pos, self.cur_kvlen, self.w.wte, self.w.wpe, self.x, cfg.eos_token_id,
-                                       self.max_length, self.prompt_len, sl, stk, slot_map=slot_map)
-        elif slot_map is None:
-            l0 = self.w.layers[0]
-            ops.decode_update(keys, self.lens[lo:hi], self.finished[lo:hi], self.out_tokens[lo:hi],
-                              self.seen[lo:hi], self.cur_tok[lo:hi], self.cur_pos[lo:hi], self.cur_kvlen[lo:hi],
-                              self.w.wte, self.w.wpe, self.x[lo:hi], cfg.eos_token_id, self.max_length,
-                              ln=(l0.ln1_g, l0.ln1_b, cfg.layer_norm_epsilon) if ln1_out is not None else None,
-                              h=ln1_out)
-        else:
-            ops.decode_update(keys, self.lens, self.finished, self.out_tokens, self.seen, self.cur_tok, self.cur_pos,
-                              self.cur_kvlen, self.w.wte, self.w.wpe, self.x, cfg.eos_token_id, self.max_length,
-                              slot_map=slot_map)
+        update, stop_args = ops.decode_update, ()
+        if mode.stop:  # the same update, which also finishes a row at a match
+            update, stop_args = ops.decode_update_stop, (rows(self.prompt_len), *self._stop_tables[mode.stop])
+        l0 = self.w.layers[0]
+        update(keys, rows(self.lens), rows(self.finished), rows(self.out_tokens), rows(self.seen), rows(self.cur_tok),
+               rows(self.cur_pos), rows(self.cur_kvlen), self.w.wte, self.w.wpe, rows(self.x), cfg.eos_token_id,
+               self.max_length, *stop_args, slot_map=slot_map,
+               ln=(l0.ln1_g, l0.ln1_b, cfg.layer_norm_epsilon) if ln1_out is not None else None, h=ln1_out)
 
-    # ------------------------------------------------------------------ sampling
+    # ------------------------------------------------------------------ generation mode
     @contextlib.contextmanager
-    def _sampling_scope(self, sampling: "SamplingParams | None"):
-        """The sampling parameters of one public call: every LM head issued (or captured) inside
-        samples with them; graphs are keyed by them.  None: greedy, exactly the calls made before."""
-        if sampling is not None:
-            self._check_sampling(sampling)
-            if self._logits is None:  # (outside any capture: graph pools must not own it)
-                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
-                                           device=self.device)
-        prev, self._sampling = self._sampling, sampling
+    def _mode_scope(self, mode: DecodeMode):
+        """The generation mode of one public call: every LM head, update and prefill issued (or
+        captured) inside runs in it, and graphs are keyed by it.  The default mode: exactly the
+        calls made before there were any."""
+        mode.check(self.tp_size, self.w.fp8)
+        self._alloc_for(mode)
+        prev, self._mode = self._mode, mode
         try:
             yield
         finally:
-            self._sampling = prev
+            self._mode = prev
 
-    @contextlib.contextmanager
-    def _controls_scope(self, controls: "GenerationControls | None"):
-        """The generation controls of one public call, like ``_sampling_scope``: every LM head and
-        update issued (or captured) inside applies them; graphs are keyed by them.  None: none,
-        exactly the calls made before."""
-        if controls is not None:
-            self._check_controls(controls)
-            # (outside any capture: graph pools must not own these)
-            if self.prompt_len is None:
-                self.prompt_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
-            if controls.bans and self._logits is None:
-                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
-                                           device=self.device)
-            if controls.stop and controls.stop not in self._stop_tables:
-                self._stop_tables[controls.stop] = ops.stop_table(controls.stop, self.device)
-        prev, self._controls = self._controls, controls
-        try:
-            yield
-        finally:
-            self._controls = prev
+    def _alloc_for(self, mode: DecodeMode):
+        """The buffers ``mode`` needs, on their first use and for the engine's life (outside any
+        capture: graph pools must not own them)."""
+        if mode.sampler is not None:
+            self._logits_scratch()
+        if mode.records_prompt_len and self.prompt_len is None:
+            self.prompt_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+        if mode.logprobs and self.out_logprob is None:
+            self.out_logprob = torch.full((self.max_batch, self.max_length), float("nan"), dtype=torch.float32,
+                                          device=self.device)
+        if mode.stop and mode.stop not in self._stop_tables:
+            self._stop_tables[mode.stop] = ops.stop_table(mode.stop, self.device)
 
-    @contextlib.contextmanager
-    def _logprobs_scope(self, logprobs: bool):
-        """Whether one public call returns log-probabilities, like ``_sampling_scope``: every LM head
-        issued (or captured) inside takes the f32-logit path (greedy: the sampler at top_k = 1) and
-        records the chosen token's log-probability (``ops.token_logprob``); graphs are keyed by it.
-        False: exactly the calls made before."""
-        if logprobs:
-            why = logprobs_unsupported(self.tp_size, self.w.fp8)
-            if why:
-                raise ValueError(why)
-            # (outside any capture: graph pools must not own these)
-            if self._logits is None:
-                self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
-                                           device=self.device)
-            if self.out_logprob is None:
-                self.out_logprob = torch.full((self.max_batch, self.max_length), float("nan"), dtype=torch.float32,
-                                              device=self.device)
-            if self.prompt_len is None:  # (collect cuts a slot's log-probabilities at its prompt's end)
-                self.prompt_len = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
-        prev, self._logprobs = self._logprobs, bool(logprobs)
-        try:
-            yield
-        finally:
-            self._logprobs = prev
-
-    def _check_controls(self, controls):
-        if not isinstance(controls, GenerationControls):
-            raise TypeError("controls: a GenerationControls (models/config.py) or None")
-        why = controls_unsupported(self.tp_size, self.w.fp8)
-        if why:
-            raise ValueError(why)
-
-    def _check_sampling(self, sampling):
-        if not isinstance(sampling, SamplingParams):
-            raise TypeError("sampling: a SamplingParams (models/config.py) or None")
-        why = sampling_unsupported(self.tp_size, self.w.fp8)
-        if why:
-            raise ValueError(why)
+    def _logits_scratch(self) -> torch.Tensor:
+        """The f32 logits rows of the sampled LM head and of ``score``."""
+        if self._logits is None:
+            self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32,
+                                       device=self.device)
+        return self._logits
 
     def reseed(self, seed: int):
         """Set the sampler's seed word and restart the request count: the next request admitted
@@ -1072,14 +936,9 @@ class HipGPT2Engine:
         return list(range(first, first + n))
 
     def _skey(self) -> tuple:
-        """What the captured graphs depend on beyond their shapes: the sampling mode, the generation
-        controls, whether log-probabilities are recorded, and whether the decode attention reads the
-        prefix store."""
-        key = () if self._sampling is None else self._sampling.shape_key
-        if self._controls is not None:
-            key = key + self._controls.shape_key
-        if self._logprobs:
-            key = key + ("logprobs",)
+        """What the captured graphs depend on beyond their shapes: the generation mode, and whether
+        the decode attention reads the prefix store."""
+        key = self._mode.graph_key
         return key + ("pfx",) if self._pfx_decode() else key
 
     def _overlap_ok(self, B: int) -> bool:
@@ -1149,11 +1008,9 @@ class HipGPT2Engine:
     def _df_ok(self, B: int) -> bool:
         from ..ops.dataflow import MAX_ROWS
 
-        # (the launch-per-op path serves row counts whose stream window outgrows the LDS ring)
-        # (sampling: the dataflow kernel's LM head is greedy; launch-per-op serves those rows.
-        # Generation controls: its commit block knows none of them; the same.  Log-probabilities: it
-        # never materialises logits; the same)
-        return (self.dataflow and self._sampling is None and self._controls is None and not self._logprobs and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
+        # (the launch-per-op path serves row counts whose stream window outgrows the LDS ring, and
+        # every mode but the default: DecodeMode.dataflow_ok)
+        return (self.dataflow and self._mode.dataflow_ok and 1 <= B <= min(MAX_ROWS, self.max_batch, self.dataflow_rows)
                 and time.monotonic() >= self._df_off_until and self._df_decoder().fits(B))
 
     def _df_run(self, B: int, steps: int, penalty: float) -> bool:
@@ -1495,9 +1352,9 @@ class HipGPT2Engine:
     def _prefill_into(self, prompts: list[list[int]], slots: list[int], penalty: float,
                       streams: list[int] | None = None):
         """Packed variable-length prefill of ``prompts`` into KV-cache slots ``slots`` (any free
-        slots of a running batch), then the first token of each (greedy, or drawn inside a
-        ``_sampling_scope``, then with the requests' stream ids ``streams``): the LM head's key rows
-        map back to their slots through decode_update's slot map."""
+        slots of a running batch), then the first token of each (greedy, or drawn in a sampling
+        mode, then with the requests' stream ids ``streams``): the LM head's key rows map back to
+        their slots through decode_update's slot map."""
         cfg, dev = self.cfg, self.device
         n = len(prompts)
         if n != len(slots) or n == 0:
@@ -1527,7 +1384,7 @@ class HipGPT2Engine:
         R = tok_np.size
         if tok_np.min() < 0 or tok_np.max() >= cfg.vocab_size:
             raise ValueError("prefill: token id out of range")
-        if self._sampling is not None:
+        if self._mode.sampling is not None:
             # the slots' stream ids, ahead of (and outside) a replayed prefill graph
             if streams is None or len(streams) != n:
                 raise ValueError("prefill: one stream id per sampled prompt")
@@ -1569,11 +1426,9 @@ class HipGPT2Engine:
             self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
         ops.seen_set(self.seen, slot_d, tokens_d)
         self.lens.index_copy_(0, idx, lens_d)
-        if self._controls is not None or self._logprobs:
-            # the prompts' lengths: what min_new_tokens and the stops count from, and where a slot's
-            # log-probabilities begin
+        if self._mode.records_prompt_len:
             self.prompt_len.index_copy_(0, idx, lens_d)
-        if self._logprobs:  # (a position the decode never reaches stays NaN)
+        if self._mode.logprobs:  # (a position the decode never reaches stays NaN)
             self.out_logprob.index_fill_(0, idx, float("nan"))
         self.finished.index_copy_(0, idx, fin_d)
         # the LM head of the first token reads the prompts' bitmaps as rows [0, n)
@@ -1726,13 +1581,7 @@ class HipGPT2Engine:
         current one).  ``controls``: the slots' generation controls; every later call that serves
         these slots passes the same.  ``logprobs``: record the chosen tokens' log-probabilities
         (``collect(..., logprobs=True)`` returns them); every later call passes the same too."""
-        if logprobs:
-            with self._logprobs_scope(True):
-                return self.admit(prompts, slots, repetition_penalty, sampling, controls)
-        if controls is not None:
-            with self._controls_scope(controls):
-                return self.admit(prompts, slots, repetition_penalty, sampling)
-        with self._sampling_scope(sampling):
+        with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
             self._prefill_into([list(p) for p in prompts], list(slots), repetition_penalty,
                                self._next_streams(len(prompts), sampling))
 
@@ -1743,13 +1592,7 @@ class HipGPT2Engine:
         sampled with ``sampling`` under the slots' stream ids (``admit``); under ``controls``, the
         ones the slots were admitted with; with ``logprobs``, recording the chosen tokens'
         log-probabilities, as the slots were admitted."""
-        if logprobs:
-            with self._logprobs_scope(True):
-                return self.decode(B, steps, repetition_penalty, sampling, controls)
-        if controls is not None:
-            with self._controls_scope(controls):
-                return self.decode(B, steps, repetition_penalty, sampling)
-        with self._sampling_scope(sampling):
+        with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
             self._decode(B, steps, repetition_penalty)
 
     def _decode(self, B: int, steps: int, repetition_penalty: float):
@@ -1761,16 +1604,20 @@ class HipGPT2Engine:
             return
         graph = self._graph_for(B, repetition_penalty) if self.use_graph else None
         kg = self._steps_per_graph_for(B) if graph is not None else 1
-        n_k = steps // kg if kg > 1 else 0
-        if n_k:
-            graph_k = self._graph_for(B, repetition_penalty, kg)
-            for _ in range(n_k):
-                graph_k.replay()
+        graph_k = self._graph_for(B, repetition_penalty, kg) if steps >= kg > 1 else None
+        self._replay(B, steps, repetition_penalty, graph, graph_k, kg)
+
+    def _replay(self, B: int, steps: int, penalty: float, graph, graph_k, kg: int):
+        """``steps`` decode steps: replays of the ``kg``-step graph ``graph_k`` (None: none) where
+        they fit, then the one-step ``graph`` (None: eager steps) for the rest."""
+        n_k = steps // kg if graph_k is not None else 0
+        for _ in range(n_k):
+            graph_k.replay()
         for _ in range(steps - n_k * kg):
             if graph is not None:
                 graph.replay()
             else:
-                self._decode_step(B, repetition_penalty)
+                self._decode_step(B, penalty)
 
     @torch.no_grad()
     def warm_decode_graphs(self, repetition_penalty: float = 1.2, max_batch: int | None = None,
@@ -1781,13 +1628,7 @@ class HipGPT2Engine:
         so a server's first burst of queries does not pay the captures.  ``sampling``: the graphs of
         that sampling mode; ``controls``: of those generation controls; ``logprobs``: the graphs that
         record log-probabilities.  Returns (graphs, seconds)."""
-        if logprobs:
-            with self._logprobs_scope(True):
-                return self.warm_decode_graphs(repetition_penalty, max_batch, sampling, controls)
-        if controls is not None:
-            with self._controls_scope(controls):
-                return self.warm_decode_graphs(repetition_penalty, max_batch, sampling)
-        with self._sampling_scope(sampling):
+        with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
             return self._warm_decode_graphs(repetition_penalty, max_batch)
 
     def _warm_decode_graphs(self, repetition_penalty: float, max_batch: int | None) -> tuple[int, float]:
@@ -1915,51 +1756,45 @@ class HipGPT2Engine:
         ``(tokens, logprobs)``; ``logprobs[i]`` holds one float per generated token of prompt i, its
         log-probability under the distribution the repetition penalty and the bans leave
         (``ops/csrc/logprob.hip``: at temperature 1, ahead of top-k / top-p)."""
-        if logprobs:
-            with self._logprobs_scope(True):
-                self._lp_rows = [[] for _ in prompts]
-                try:
-                    return self.generate(prompts, max_length, repetition_penalty, stats, sampling, controls), \
-                        self._lp_rows
-                finally:
-                    self._lp_rows = None
-        if controls is not None:
-            with self._controls_scope(controls):
-                return self.generate(prompts, max_length, repetition_penalty, stats, sampling)
-        if sampling is None:
-            return self._generate(prompts, max_length, repetition_penalty, stats, None, list(range(len(prompts))))
-        with self._sampling_scope(sampling):
-            self.reseed(sampling.seed)
-            self._rng_count = len(prompts)
-            return self._generate(prompts, max_length, repetition_penalty, stats, list(range(len(prompts))),
-                                  list(range(len(prompts))))
+        with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
+            streams = None
+            if sampling is not None:
+                self.reseed(sampling.seed)
+                self._rng_count = len(prompts)
+                streams = list(range(len(prompts)))
+            toks, lps = self._generate(prompts, max_length, repetition_penalty, stats, streams)
+        return (toks, lps) if logprobs else toks
 
     def _generate(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
-                  stats: GenerateStats | None, streams: list[int] | None, rows: list[int]) -> list[list[int]]:
-        """``rows``: the indices of ``prompts`` in the public call (where their log-probabilities go)."""
+                  stats: GenerateStats | None, streams: list[int] | None) -> tuple[list[list[int]], list[list[float]]]:
+        """(tokens, log-probabilities) per prompt in the mode of the scope around it; a prompt that
+        only passes through, or a mode without log-probabilities, gives ``[]`` for the second."""
         T = self.max_length if max_length is None else max_length
         if T != self.max_length:
             raise ValueError(f"engine built for max_length={self.max_length}, got {T}")
         n = len(prompts)
         if n == 0:
-            return []
+            return [], []
 
         def pick(idx):
             return None if streams is None else [streams[i] for i in idx]
 
         done, run_idx, prompts = passthrough(prompts, T, self.cfg.eos_token_id)
         if len(run_idx) < n:
-            sub = self._generate([prompts[i] for i in run_idx], max_length, repetition_penalty, stats,
-                                 pick(run_idx), [rows[i] for i in run_idx]) if run_idx else []
-            for i, o in zip(run_idx, sub):
-                done[i] = o
-            return done
+            lps: list[list[float]] = [[] for _ in prompts]
+            if run_idx:
+                sub = self._generate([prompts[i] for i in run_idx], max_length, repetition_penalty, stats, pick(run_idx))
+                for i, o, lp in zip(run_idx, *sub):
+                    done[i], lps[i] = o, lp
+            return done, lps
         if n > self.max_batch:
-            out: list[list[int]] = []
+            out, lps = [], []
             for i in range(0, n, self.max_batch):
-                out += self._generate(prompts[i: i + self.max_batch], max_length, repetition_penalty, stats,
-                                      pick(range(i, min(n, i + self.max_batch))), rows[i: i + self.max_batch])
-            return out
+                sub = self._generate(prompts[i: i + self.max_batch], max_length, repetition_penalty, stats,
+                                     pick(range(i, min(n, i + self.max_batch))))
+                out += sub[0]
+                lps += sub[1]
+            return out, lps
         B = min(_bucket(n), self.max_batch)  # (prompts are passthrough()'s normalised copies)
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
@@ -1978,16 +1813,8 @@ class HipGPT2Engine:
                 lens = self.lens[:n].cpu().tolist()
                 toks = self.out_tokens[:n].cpu().numpy()
                 res = [toks[b, : lens[b]].tolist() for b in range(n)]
-                if stats is not None:
-                    ev2.synchronize()
-                    stats.batch += n
-                    stats.prompt_tokens += sum(len(p) for p in prompts)
-                    stats.new_tokens += sum(lens[b] - len(prompts[b]) for b in range(n))
-                    stats.prefill_ms += ev0.elapsed_time(ev1)
-                    stats.decode_ms += ev1.elapsed_time(ev2)
-                    stats.steps += st[4]
-                    stats.graph = False
-                return res
+                self._add_stats(stats, prompts, lens, (ev0, ev1, ev2), st[4], False)
+                return res, [[] for _ in res]  # (the dataflow decode serves the default mode only)
             # aborted before its commit: the rows are exactly as the prefill left them -- decode
             # them launch-per-op below
         graph = self._graph_for(B, repetition_penalty) if (self.use_graph and steps_max > 0) else None
@@ -2003,16 +1830,7 @@ class HipGPT2Engine:
         pending = None
         while steps < steps_max:
             chunk = min(self.check_every, steps_max - steps)
-            done_k = 0
-            if graph_k is not None:
-                for _ in range(chunk // kg):
-                    graph_k.replay()
-                done_k = chunk // kg * kg
-            for _ in range(chunk - done_k):
-                if graph is not None:
-                    graph.replay()
-                else:
-                    self._decode_step(B, repetition_penalty)
+            self._replay(B, chunk, repetition_penalty, graph, graph_k, kg)
             steps += chunk
             if steps >= steps_max:
                 break
@@ -2036,20 +1854,29 @@ class HipGPT2Engine:
         res = toks.tolist()
         for row, ln in zip(res, lens):
             del row[ln:]
-        if self._logprobs:
+        if self._mode.logprobs:
             lp = self.out_logprob[:n].cpu().numpy().tolist()
-            for b in range(n):
-                self._lp_rows[rows[b]] = lp[b][len(prompts[b]): lens[b]]
-        if stats is not None:
-            ev2.synchronize()
-            stats.batch += n
-            stats.prompt_tokens += sum(len(p) for p in prompts)
-            stats.new_tokens += sum(lens[b] - len(prompts[b]) for b in range(n))
-            stats.prefill_ms += ev0.elapsed_time(ev1)
-            stats.decode_ms += ev1.elapsed_time(ev2)
-            stats.steps += steps
-            stats.graph = graph is not None
-        return res
+            lps = [lp[b][len(prompts[b]): lens[b]] for b in range(n)]
+        else:
+            lps = [[] for _ in res]
+        self._add_stats(stats, prompts, lens, (ev0, ev1, ev2), steps, graph is not None)
+        return res, lps
+
+    @staticmethod
+    def _add_stats(stats: GenerateStats | None, prompts, lens, events, steps: int, graph: bool):
+        """One batch of ``_generate`` into ``stats`` (None: nothing): ``events`` are the ones
+        recorded ahead of the prefill, between it and the decode, and behind the decode."""
+        if stats is None:
+            return
+        ev0, ev1, ev2 = events
+        ev2.synchronize()
+        stats.batch += len(prompts)
+        stats.prompt_tokens += sum(len(p) for p in prompts)
+        stats.new_tokens += sum(ln - len(p) for ln, p in zip(lens, prompts))
+        stats.prefill_ms += ev0.elapsed_time(ev1)
+        stats.decode_ms += ev1.elapsed_time(ev2)
+        stats.steps += steps
+        stats.graph = graph
 
     @torch.no_grad()
     def score(self, sequences: list[list[int]]) -> list[list[float]]:
@@ -2077,8 +1904,7 @@ class HipGPT2Engine:
             raise ValueError("score: token id out of range")
         if int(self.finished.min().item()) == 0:
             raise RuntimeError("score: a slot is unfinished; score between batches")
-        if self._logits is None:  # (outside any capture: graph pools must not own it)
-            self._logits = torch.empty(self.max_batch, self.w.lm_head.shape[0], dtype=torch.float32, device=dev)
+        logits = self._logits_scratch()
         tok_np, pos_np, slot_np, last_np, lens_np, sl_np = pack_prompts(seqs, list(range(n)))
         # the packed rows that have a next token (all but each sequence's last), and that token
         has_next = np.ones(tok_np.size, dtype=bool)
@@ -2094,7 +1920,7 @@ class HipGPT2Engine:
         out = torch.empty(R, dtype=torch.float32, device=dev)
         for c0 in range(0, R, self.max_batch):
             m = min(self.max_batch, R - c0)
-            z = self._logits[:m]
+            z = logits[:m]
             if self.ps_lm and m >= self.PS_LM_MIN_ROWS:
                 ops.gemm_ps(h[c0:c0 + m], self.lm_head_sh, ops.EPI_PARTIAL, out=z.unsqueeze(0), split_k=1)
             else:

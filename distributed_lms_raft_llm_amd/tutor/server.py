@@ -747,43 +747,26 @@ def main(argv=None):
         sampling = sampling_from_args(args)
     except ValueError as e:
         ap.error(str(e))
-    if sampling is not None:
-        from ..engine.gpt2_engine import sampling_unsupported
+    from ..engine import mode as engine_mode
 
-        why = sampling_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
+    want_controls = bool(args.no_repeat_ngram_size or args.min_new_tokens or args.stop)
+    logprobs = args.logprobs or args.min_mean_logprob is not None
+    for wanted, option, unsupported in (
+            (sampling is not None, "--sample", engine_mode.sampling_unsupported),
+            (args.kv_dtype == "fp8", "--kv-dtype fp8", engine_mode.kv_fp8_unsupported),
+            (args.prefix_cache == "on", "--prefix-cache on", engine_mode.prefix_unsupported),
+            (want_controls, "--no-repeat-ngram-size / --min-new-tokens / --stop", engine_mode.controls_unsupported),
+            (logprobs, "--logprobs / --min-mean-logprob", engine_mode.logprobs_unsupported)):
+        why = wanted and unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
         if why:
-            ap.error(f"--sample: {why}")
-    if args.kv_dtype == "fp8":
-        from ..engine.gpt2_engine import kv_fp8_unsupported
-
-        why = kv_fp8_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
-        if why:
-            ap.error(f"--kv-dtype fp8: {why}")
-    if args.prefix_cache == "on":
-        from ..engine.gpt2_engine import prefix_unsupported
-
-        why = prefix_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
-        if why:
-            ap.error(f"--prefix-cache on: {why}")
+            ap.error(f"{option}: {why}")
     controls = None
-    if args.no_repeat_ngram_size or args.min_new_tokens or args.stop:
-        from ..engine.gpt2_engine import controls_unsupported
-
-        why = controls_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
-        if why:
-            ap.error(f"--no-repeat-ngram-size / --min-new-tokens / --stop: {why}")
+    if want_controls:
         try:  # (the stop texts are encoded here, once, with the tokenizer the server detokenises with)
             controls = controls_from_args(args, GPT2BPE(args.vocab, args.merges,
                                                         eos_token_id=gpt2_config(args.model).eos_token_id))
         except ValueError as e:
             ap.error(str(e))
-    logprobs = args.logprobs or args.min_mean_logprob is not None
-    if logprobs:
-        from ..engine.gpt2_engine import logprobs_unsupported
-
-        why = logprobs_unsupported(args.tp or int(os.environ.get("WORLD_SIZE", "1")), args.weight_dtype == "fp8")
-        if why:
-            ap.error(f"--logprobs / --min-mean-logprob: {why}")
     mode = {} if sampling is None else {"sampling": sampling}
     mode.update(_controls_kw(controls))
     mode.update(_logprobs_kw(logprobs))

@@ -359,6 +359,8 @@ def test_engine_no_repeat_ngram(model, engines, kind, n):
 def test_controls_bypass_the_dataflow_decode(model, engines, monkeypatch):
     """(f) one row: greedy decodes on the persistent dataflow kernel (where the engine has it), a call
     with controls -- banning or stop-only -- never launches it."""
+    from distributed_lms_raft_llm_amd.engine.mode import DecodeMode
+
     cfg, _, _ = model
     eng = engines("small")
     eng.use_graph = True
@@ -367,7 +369,7 @@ def test_controls_bypass_the_dataflow_decode(model, engines, monkeypatch):
     monkeypatch.setattr(eng, "_df_run", lambda *a: launches.append(a) or run(*a))
     prompts = _prompts(cfg, 1, cc.prompt_seed(1))
     for ct in (_gc(no_repeat_ngram_size=2), _gc(min_new_tokens=2), _gc(stop=((1, 2),))):
-        with eng._controls_scope(ct):
+        with eng._mode_scope(DecodeMode(controls=ct)):
             assert not eng._df_ok(1)
         eng.generate(prompts, repetition_penalty=PEN, controls=ct)
         eng.decode(1, 2, PEN, controls=ct)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import logprob_cases as lc
+from distributed_lms_raft_llm_amd.engine.mode import DecodeMode
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -256,7 +257,7 @@ def test_engine_logprobs(model, engines, kind, n):
         assert eng.generate(prompts, repetition_penalty=PEN) == greedy
         assert all(a is b for a, b in zip((eng._logits, eng.out_logprob, eng.prompt_len), held))
         assert [t.data_ptr() for t in held] == ptrs and set(eng._graphs) == graphs
-        assert not eng._logprobs and eng._lp_rows is None
+        assert eng._mode == DecodeMode()
         res[graph] = (toks, lps)
     eng.use_graph = True
     assert res[True][0] == res[False][0], "graph replay and eager disagree on the tokens"
@@ -273,7 +274,7 @@ def test_logprobs_bypass_the_dataflow_decode(model, engines, monkeypatch):
     run = eng._df_run
     monkeypatch.setattr(eng, "_df_run", lambda *a: launches.append(a) or run(*a))
     prompts = lc.prompts(cfg, 1)
-    with eng._logprobs_scope(True):
+    with eng._mode_scope(DecodeMode(logprobs=True)):
         assert not eng._df_ok(1)
     eng.generate(prompts, repetition_penalty=PEN, logprobs=True)
     eng.decode(1, 2, PEN, logprobs=True)

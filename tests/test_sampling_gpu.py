@@ -183,6 +183,7 @@ def test_engine_sampling(model, engines, kind, n):
 def test_sampling_bypasses_the_dataflow_decode(model, engines, monkeypatch):
     """One row: greedy decodes on the persistent dataflow kernel (where the engine has it), a sampled
     call never launches it."""
+    from distributed_lms_raft_llm_amd.engine.mode import DecodeMode
     from distributed_lms_raft_llm_amd.models.config import SamplingParams
 
     cfg, _, _ = model
@@ -191,7 +192,7 @@ def test_sampling_bypasses_the_dataflow_decode(model, engines, monkeypatch):
     launches = []
     run = eng._df_run
     monkeypatch.setattr(eng, "_df_run", lambda *a: launches.append(a) or run(*a))
-    with eng._sampling_scope(SamplingParams()):
+    with eng._mode_scope(DecodeMode(sampling=SamplingParams())):
         assert not eng._df_ok(1)
     prompts = _prompts(cfg, 1)
     eng.generate(prompts, repetition_penalty=PEN, sampling=SamplingParams(0.7, 50, 0.9, 1))
