@@ -1349,36 +1349,35 @@ class HipGPT2Engine:
         """The tokens of the prefix in the store (None: no prefix set)."""
         return None if self._pfx_tokens is None else list(self._pfx_tokens)
 
+    def _check_completions(self, k: int) -> int:
+        """``n`` of a public call: an integer in [1, max_batch]; more than one only in a sampling mode
+        (n equal greedy answers is a mistake, not a feature)."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"n: a positive integer, got {k!r}")
+        if k > self.max_batch:
+            raise ValueError(f"n = {k} completions per prompt do not fit max_batch = {self.max_batch} slots")
+        if k > 1 and self._mode.sampling is None:
+            raise ValueError("n > 1 needs sampling=: greedy completions of one prompt are all equal")
+        return k
+
     def _prefill_into(self, prompts: list[list[int]], slots: list[int], penalty: float,
-                      streams: list[int] | None = None):
+                      streams: list[int] | None = None, k: int = 1):
         """Packed variable-length prefill of ``prompts`` into KV-cache slots ``slots`` (any free
         slots of a running batch), then the first token of each (greedy, or drawn in a sampling
         mode, then with the requests' stream ids ``streams``): the LM head's key rows map back to
-        their slots through decode_update's slot map."""
+        their slots through decode_update's slot map.  ``k`` > 1 (best of n): ``slots`` lists k per
+        prompt, prompt i owning ``slots[i * k: (i + 1) * k]``; the prompt is prefilled once, into the
+        first of them (its parent), whose K/V and bookkeeping are forked into the other k - 1 before
+        the LM head draws k first tokens, one per slot and stream."""
+        if k > 1:
+            return self._prefill_forked(prompts, slots, penalty, streams, k)
         cfg, dev = self.cfg, self.device
         n = len(prompts)
         if n != len(slots) or n == 0:
             raise ValueError("prefill: one slot per prompt")
         if min(slots) < 0 or max(slots) >= self.max_batch or len(set(slots)) != n:
             raise ValueError(f"prefill: slots must be distinct and in [0, {self.max_batch})")
-        T = self.max_length
-        lens = [len(p) for p in prompts]
-        if min(lens) < 1 or max(lens) > T:
-            raise ValueError("prefill: prompt lengths must be in [1, max_length]")
-        # prompt-prefix cache: the prompts that start with the stored prefix run their suffix rows
-        # only (one packed prefill with the others); pfx_np is None on an engine without a store
-        pfx = pfx_np = None
-        if self.prefix_capacity:
-            pfx = split_prefix(prompts, self._pfx_tokens)
-            pfx_np = np.asarray(pfx, dtype=np.int64)
-            if self._pfx_tokens is not None:
-                hits, rows = sum(1 for k in pfx if k), sum(pfx)
-                self.prefix_prompts += n
-                self.prefix_hits += hits
-                self.prefix_rows_skipped += rows
-                METRICS.inc("engine_prefix_prompts", n)
-                METRICS.inc("engine_prefix_hits", hits)
-                METRICS.inc("engine_prefix_rows_skipped", rows)
+        pfx, pfx_np = self._split_prompts(prompts)
         # packed token / position / slot arrays built with numpy (pack_prompts)
         tok_np, pos_np, slot_np, last_np, lens_np, sl_np = pack_prompts(prompts, slots, pfx)
         R = tok_np.size
@@ -1398,11 +1397,75 @@ class HipGPT2Engine:
         self._prefill_core(tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, ops.AttnTiles(sl_np.tolist(), dev),
                            penalty, pfx_d)
 
-    def _prefill_core(self, tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty: float, pfx_d=None):
+    def _split_prompts(self, prompts: list[list[int]]):
+        """Length check, then the prompt-prefix split of a prefill: the prompts that start with the
+        stored prefix run their suffix rows only (one packed prefill with the others).  Counts
+        prompts (not completions) into the prefix-hit counters.  Returns (pfx list, pfx int64 array),
+        both None on an engine without a store."""
+        n = len(prompts)
+        lens = [len(p) for p in prompts]
+        if min(lens) < 1 or max(lens) > self.max_length:
+            raise ValueError("prefill: prompt lengths must be in [1, max_length]")
+        pfx = pfx_np = None
+        if self.prefix_capacity:
+            pfx = split_prefix(prompts, self._pfx_tokens)
+            pfx_np = np.asarray(pfx, dtype=np.int64)
+            if self._pfx_tokens is not None:
+                hits, rows = sum(1 for k in pfx if k), sum(pfx)
+                self.prefix_prompts += n
+                self.prefix_hits += hits
+                self.prefix_rows_skipped += rows
+                METRICS.inc("engine_prefix_prompts", n)
+                METRICS.inc("engine_prefix_hits", hits)
+                METRICS.inc("engine_prefix_rows_skipped", rows)
+        return pfx, pfx_np
+
+    def _prefill_forked(self, prompts: list[list[int]], slots: list[int], penalty: float,
+                        streams: list[int] | None, k: int):
+        """``_prefill_into`` for k > 1 completions per prompt: the packed arrays and the prefix split
+        see the parents only; the per-slot arrays (last row, slot, length, prefix) repeat each
+        prompt's words k times, and the fork table lists (parent, child, prompt length) per child."""
+        cfg, dev = self.cfg, self.device
+        n = len(prompts)
+        N = n * k
+        if n == 0 or len(slots) != N:
+            raise ValueError(f"prefill: {k} slots per prompt")
+        if min(slots) < 0 or max(slots) >= self.max_batch or len(set(slots)) != N:
+            raise ValueError(f"prefill: slots must be distinct and in [0, {self.max_batch})")
+        if self._mode.sampling is None or streams is None or len(streams) != N:
+            raise ValueError("prefill: one stream id per sampled completion")
+        slots_np = np.asarray(slots, dtype=np.int64)
+        groups = slots_np.reshape(n, k)
+        pfx, pfx_np = self._split_prompts(prompts)
+        tok_np, pos_np, slot_np, last_np, lens_np, sl_np = pack_prompts(prompts, groups[:, 0].tolist(), pfx)
+        R = tok_np.size
+        if tok_np.min() < 0 or tok_np.max() >= cfg.vocab_size:
+            raise ValueError("prefill: token id out of range")
+        self.rng_stream.index_copy_(0, _to_device(slots_np, dev, np.int64),
+                                    _to_device(np.asarray(streams, dtype=np.uint64).view(np.int64), dev, np.int64))
+        fork_np = (np.repeat(groups[:, 0], k - 1), groups[:, 1:].reshape(-1), np.repeat(lens_np, k - 1))
+        ops.check_fork_pairs(*fork_np, self.max_batch)
+        if self._prefill_graph_ok(R, n, k):
+            return self._prefill_graphed(tok_np, pos_np, slot_np, last_np, slots_np, lens_np, penalty, pfx_np, fork_np)
+        tokens_d, pos_d, slot_d, last_d, slots_d, lens_d = (
+            _to_device(a, dev) for a in (tok_np, pos_np, slot_np, np.repeat(last_np, k), slots_np,
+                                         np.repeat(lens_np, k)))
+        pfx_d = None if pfx_np is None else _to_device(np.repeat(pfx_np, k), dev)
+        self._prefill_core(tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, ops.AttnTiles(sl_np.tolist(), dev),
+                           penalty, pfx_d, tuple(_to_device(a, dev) for a in fork_np))
+
+    def _prefill_core(self, tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty: float, pfx_d=None,
+                      fork=None):
         """Device side of a packed prefill (no host synchronisation: also captured as a graph).
         ``pfx_d`` (engines with a prefix store): per prompt the number of leading tokens whose K/V
         come from the store -- the packed rows are then the suffixes (positions from ``pfx``), the
-        bookkeeping still sees whole prompts, and the store's rows are copied into the slots."""
+        bookkeeping still sees whole prompts, and the store's rows are copied into the slots.
+        ``fork`` (best of n: ``(src, dst, lens)`` per child): ``last_d`` / ``slots_d`` / ``lens_d`` /
+        ``pfx_d`` then hold one word per slot, parents and children, while the packed rows are the
+        parents' alone (``_prefill_core_forked``)."""
+        if fork is not None:
+            return self._prefill_core_forked(tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty, pfx_d,
+                                             fork)
         cfg = self.cfg
         T = self.max_length
         n = slots_d.numel()
@@ -1443,6 +1506,47 @@ class HipGPT2Engine:
         # first token: argmax rows are prompts (seen rows gathered), updates land in their slots
         self._lm_head_and_update(hl, n, penalty, seen=seen_d, hscale=hsc_l, slot_map=slots_d)
 
+    def _prefill_core_forked(self, tokens_d, pos_d, slot_d, last_d, slots_d, lens_d, tiles, penalty: float, pfx_d,
+                             fork):
+        """``_prefill_core`` for k completions per prompt.  The per-slot bookkeeping is written for all
+        the slots (the children get their parents' ``out_tokens`` and ``seen`` rows), the layers run
+        the parents' packed rows, one ``ops.kv_fork`` copies each parent's prompt keys -- the store's
+        rows included, so a child's ``slot_pfx`` equals its parent's -- into its children, and the LM
+        head draws one first token per slot from k equal rows per prompt."""
+        cfg = self.cfg
+        src_d, dst_d, flens_d = fork
+        N = slots_d.numel()
+        n = N - dst_d.numel()  # prompts
+        idx = slots_d.long()
+        src_l, dst_l = src_d.long(), dst_d.long()
+        self.out_tokens.index_fill_(0, idx, 0)
+        if pfx_d is None:
+            self.seen.index_fill_(0, idx, 0)
+        else:
+            C = self.prefix_capacity
+            share = pfx_d[:, None] > torch.arange(C, dtype=torch.int32, device=self.device)[None, :]
+            self.out_tokens[:, :C].index_copy_(0, idx, self._pfx_tok_d[None, :] * share)
+            self.seen.index_copy_(0, idx, self._pfx_seen[None, :] * (pfx_d[:, None] > 0))
+            self.slot_pfx.index_copy_(0, idx, pfx_d)
+            k = N // n
+            ops.kv_prefix_fill(self.kv, self.pfx_store, slots_d.view(n, k)[:, 0].contiguous(),
+                               pfx_d.view(n, k)[:, 0].contiguous())
+        self.out_tokens.index_put_((slot_d.long(), pos_d.long()), tokens_d)
+        ops.seen_set(self.seen, slot_d, tokens_d)
+        self.out_tokens.index_copy_(0, dst_l, self.out_tokens.index_select(0, src_l))
+        self.seen.index_copy_(0, dst_l, self.seen.index_select(0, src_l))
+        self.lens.index_copy_(0, idx, lens_d)
+        if self._mode.records_prompt_len:
+            self.prompt_len.index_copy_(0, idx, lens_d)
+        if self._mode.logprobs:
+            self.out_logprob.index_fill_(0, idx, float("nan"))
+        self.finished.index_copy_(0, idx, (lens_d >= self.max_length).to(torch.int32))
+        seen_d = self.seen.index_select(0, idx)
+        x = self._prefill_layers(tokens_d, pos_d, slot_d, tiles)
+        ops.kv_fork(self.kv, src_d, dst_d, flens_d, host_checked=True)  # (_prefill_forked checked the table)
+        hl = ops.layernorm_gather(x, last_d, self.w.lnf_g, self.w.lnf_b, cfg.layer_norm_epsilon)
+        self._lm_head_and_update(hl, N, penalty, seen=seen_d, slot_map=slots_d)
+
     def _prefill_layers(self, tokens_d, pos_d, slot_d, tiles) -> torch.Tensor:
         """Embedding and every block of a packed prefill (K/V scattered into the rows' slots at
         their positions); returns the final residual rows, ahead of ln_f."""
@@ -1471,12 +1575,17 @@ class HipGPT2Engine:
     PREFILL_GRAPH_MAX_ROWS = 4096
     PREFILL_GRAPH_CACHE = 32
 
-    def _prefill_graph_ok(self, R: int, n: int) -> bool:
+    def _pkey(self, R: int, n: int, k: int = 1) -> tuple:
+        """The key of a prefill graph: (packed rows, prompts), the completions per prompt where there
+        are more than one, then the mode key."""
+        return ((R, n) if k == 1 else (R, n, k)) + self._skey()
+
+    def _prefill_graph_ok(self, R: int, n: int, k: int = 1) -> bool:
         if not (self.use_graph and self.prefill_graphs and R <= self.PREFILL_GRAPH_MAX_ROWS):
             return False
         if self.tp_size > 1 and not self._tp_capturable(R):
             return False
-        key = (R, n) + self._skey()
+        key = self._pkey(R, n, k)
         if key in self._pgraphs:
             return True
         if len(self._pseen) > 8192:  # shapes seen once: a bounded memory of candidates
@@ -1493,18 +1602,28 @@ class HipGPT2Engine:
             return False
         return R * self.cfg.n_embd * 4 <= self.xgmi.slab_bytes or dist.get_backend(self.tp_group) == "nccl"
 
-    def _prefill_graphed(self, tok, pos, slot, last, slots, lens, penalty: float, pfx=None):
+    def _prefill_graphed(self, tok, pos, slot, last, slots, lens, penalty: float, pfx=None, fork=None):
         """``pfx`` (engines with a prefix store): per prompt the leading tokens taken from the store;
         the packed rows and the tiles are then those of the suffixes, and ``pfx`` is staged with the
         other per-prompt words (one graph serves every mix of sharing and other prompts of its
-        (rows, prompts) shape)."""
+        (rows, prompts) shape).  ``fork`` (best of n: the ``(src, dst, lens)`` arrays of the children):
+        ``slots`` then lists every slot, k per prompt, while ``last`` / ``lens`` / ``pfx`` stay per prompt;
+        the per-slot words are staged k times over and the fork table behind the tiles."""
+        if fork is not None:
+            P, k = lens.size, slots.size // lens.size
+            tile_lens, tile_pfx = lens, pfx
+            last, lens = np.repeat(last, k), np.repeat(lens, k)
+            pfx = None if pfx is None else np.repeat(pfx, k)
+        else:
+            P, k, tile_lens, tile_pfx = slots.size, 1, lens, pfx
         R, n = tok.size, slots.size
-        key = (R, n) + self._skey()
-        TB = R // 16 + n  # >= the tile count of any R rows in n prompts
-        npp = 3 if pfx is None else 4  # staged words per prompt
+        key = self._pkey(R, P, k)
+        TB = R // 16 + P  # >= the tile count of any R rows in P prompts
+        npp = 3 if pfx is None else 4  # staged words per slot
+        nf = 0 if fork is None else fork[0].size  # children
         st = self._pgraphs.get(key)
         if st is None:
-            words = 3 * R + npp * n + 2 * TB
+            words = 3 * R + npp * n + 2 * TB + 3 * nf
             st = dict(host=torch.empty(words, dtype=torch.int32).pin_memory(),
                       dev=torch.empty(words, dtype=torch.int32, device=self.device), copied=torch.cuda.Event(),
                       graph=None, penalty=penalty)
@@ -1514,37 +1633,42 @@ class HipGPT2Engine:
         hbuf[:R], hbuf[R:2 * R], hbuf[2 * R:3 * R] = tok, pos, slot
         o = 3 * R
         hbuf[o:o + n], hbuf[o + n:o + 2 * n], hbuf[o + 2 * n:o + 3 * n] = last, slots, lens
-        rl = lens  # rows each prompt runs: its suffix
         if pfx is not None:
             hbuf[o + 3 * n:o + 4 * n] = pfx
-            rl = lens - pfx
+        of = o + npp * n + 2 * TB  # the fork table, behind the tiles
+        if fork is not None:
+            hbuf[of:of + nf], hbuf[of + nf:of + 2 * nf], hbuf[of + 2 * nf:] = fork
+        rl = tile_lens if tile_pfx is None else tile_lens - tile_pfx  # rows each prompt runs: its suffix
         nt = (rl + 15) // 16
-        seq = np.repeat(np.arange(n), nt)
+        seq = np.repeat(np.arange(P), nt)
         k = np.arange(int(nt.sum())) - np.repeat(np.cumsum(nt) - nt, nt)
         starts = np.cumsum(rl) - rl
         tt = np.empty((TB, 2), dtype=np.int64)
         tt[: len(seq), 0] = starts[seq] + 16 * k
         tt[: len(seq), 1] = np.minimum(16, rl[seq] - 16 * k)
         tt[len(seq):] = tt[len(seq) - 1]  # padding tiles repeat the last one (identical writes)
-        hbuf[o + npp * n:] = tt.reshape(-1)
+        hbuf[o + npp * n:of] = tt.reshape(-1)
         st["dev"].copy_(st["host"], non_blocking=True)
         st["copied"].record()
         if st["graph"] is None or st["penalty"] != penalty:
             d = st["dev"]
             tiles = ops.AttnTiles.__new__(ops.AttnTiles)
-            tiles.rows, tiles.n, tiles.t = R, TB, d[o + npp * n:].view(TB, 2)
+            tiles.rows, tiles.n, tiles.t = R, TB, d[o + npp * n:of].view(TB, 2)
             args = (d[:R], d[R:2 * R], d[2 * R:3 * R], d[o:o + n], d[o + n:o + 2 * n], d[o + 2 * n:o + 3 * n], tiles,
                     penalty, None if pfx is None else d[o + 3 * n:o + 4 * n])
+            if fork is not None:
+                args += ((d[of:of + nf], d[of + nf:of + 2 * nf], d[of + 2 * nf:]),)
             g = torch.cuda.CUDAGraph()
             with capture_guard(), torch.cuda.graph(g):
                 self._prefill_core(*args)
             st["graph"], st["penalty"] = g, penalty
         st["graph"].replay()
 
-    def _prefill(self, prompts: list[list[int]], B: int, penalty: float, streams: list[int] | None = None):
-        """Static batch: prompts into slots [0, n), slots [n, B) inert."""
-        self._reset_slots(len(prompts), B)
-        self._prefill_into(prompts, list(range(len(prompts))), penalty, streams)
+    def _prefill(self, prompts: list[list[int]], B: int, penalty: float, streams: list[int] | None = None,
+                 k: int = 1):
+        """Static batch: prompts (``k`` completions each) into slots [0, n * k), the rest of [0, B) inert."""
+        self._reset_slots(len(prompts) * k, B)
+        self._prefill_into(prompts, list(range(len(prompts) * k)), penalty, streams, k)
 
     @torch.no_grad()
     def prefill_last_hidden(self, prompts: list[list[int]]) -> torch.Tensor:
@@ -1574,16 +1698,22 @@ class HipGPT2Engine:
     @torch.no_grad()
     def admit(self, prompts: list[list[int]], slots: list[int], repetition_penalty: float = 1.2,
               sampling: SamplingParams | None = None, controls: GenerationControls | None = None,
-              logprobs: bool = False):
+              logprobs: bool = False, n: int = 1):
         """Prefill new sequences into free ``slots`` of the running batch (first token included).
         ``sampling``: draw their tokens instead; each takes the next stream id (the count of requests
         admitted since the seed was last set: ``reseed``, or a ``sampling.seed`` other than the
         current one).  ``controls``: the slots' generation controls; every later call that serves
         these slots passes the same.  ``logprobs``: record the chosen tokens' log-probabilities
-        (``collect(..., logprobs=True)`` returns them); every later call passes the same too."""
+        (``collect(..., logprobs=True)`` returns them); every later call passes the same too.
+        ``n`` > 1 (needs ``sampling``): n completions per prompt from one prefill.  ``slots`` lists
+        ``n * len(prompts)`` distinct slots, prompt i owning ``slots[i * n: (i + 1) * n]``, the first of
+        them its parent: the prompt is prefilled into the parent and forked into the others
+        (``ops.kv_fork``); completion j of the i-th prompt draws on stream ``first + i * n + j``.  The
+        decode does not know about groups: every slot is an ordinary sequence from here on."""
         with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
+            n = self._check_completions(n)
             self._prefill_into([list(p) for p in prompts], list(slots), repetition_penalty,
-                               self._next_streams(len(prompts), sampling))
+                               self._next_streams(n * len(prompts), sampling), n)
 
     @torch.no_grad()
     def decode(self, B: int, steps: int, repetition_penalty: float = 1.2, sampling: SamplingParams | None = None,
@@ -1748,30 +1878,63 @@ class HipGPT2Engine:
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
                  stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
-                 controls: GenerationControls | None = None, logprobs: bool = False):
+                 controls: GenerationControls | None = None, logprobs: bool = False, n: int = 1):
         """Full sequences (prompt echoed) of ``prompts``: greedy, or with ``sampling`` drawn under
         ``sampling.seed`` with prompt i on stream i -- set anew on every call, so equal calls return
         equal outputs.  ``controls`` (a ``GenerationControls``): n-gram blocking, a minimum length and
         stop sequences, applied on the device inside the decode loop.  ``logprobs``: returns
         ``(tokens, logprobs)``; ``logprobs[i]`` holds one float per generated token of prompt i, its
         log-probability under the distribution the repetition penalty and the bans leave
-        (``ops/csrc/logprob.hip``: at temperature 1, ahead of top-k / top-p)."""
+        (``ops/csrc/logprob.hip``: at temperature 1, ahead of top-k / top-p).
+        ``n`` > 1 (needs ``sampling``; at most ``max_batch``): per prompt a list of n sequences from one
+        prefill, completion j of prompt i drawn on stream ``i * n + j`` (``tokens`` and ``logprobs``
+        nested the same way); a prompt that only passes through yields n copies; more than
+        ``max_batch`` completions run in chunks of whole groups."""
         with self._mode_scope(DecodeMode(sampling, controls, bool(logprobs))):
+            n = self._check_completions(n)
             streams = None
             if sampling is not None:
                 self.reseed(sampling.seed)
-                self._rng_count = len(prompts)
-                streams = list(range(len(prompts)))
-            toks, lps = self._generate(prompts, max_length, repetition_penalty, stats, streams)
+                self._rng_count = n * len(prompts)
+                streams = list(range(n * len(prompts)))
+            if n == 1:
+                toks, lps = self._generate(prompts, max_length, repetition_penalty, stats, streams)
+            else:
+                toks, lps = self._generate_groups(prompts, max_length, repetition_penalty, stats, n)
         return (toks, lps) if logprobs else toks
 
-    def _generate(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
-                  stats: GenerateStats | None, streams: list[int] | None) -> tuple[list[list[int]], list[list[float]]]:
-        """(tokens, log-probabilities) per prompt in the mode of the scope around it; a prompt that
-        only passes through, or a mode without log-probabilities, gives ``[]`` for the second."""
+    def _generate_groups(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
+                         stats: GenerateStats | None, k: int):
+        """``_generate`` with k > 1 completions per prompt, nested per prompt: the prompts that run go
+        through ``_generate`` in chunks of ``max_batch // k`` whole groups, completion j of prompt i on
+        stream ``i * k + j``; a prompt that only passes through yields k copies."""
         T = self.max_length if max_length is None else max_length
         if T != self.max_length:
             raise ValueError(f"engine built for max_length={self.max_length}, got {T}")
+        done, run_idx, norm = passthrough(prompts, T, self.cfg.eos_token_id)
+        toks = [None if o is None else [list(o) for _ in range(k)] for o in done]
+        lps = [[[] for _ in range(k)] for _ in done]
+        per = self.max_batch // k
+        for c in range(0, len(run_idx), per):
+            idx = run_idx[c: c + per]
+            sub = self._generate([norm[i] for i in idx], max_length, repetition_penalty, stats,
+                                 [i * k + j for i in idx for j in range(k)], k)
+            for m, i in enumerate(idx):
+                toks[i], lps[i] = sub[0][m * k: (m + 1) * k], sub[1][m * k: (m + 1) * k]
+        return toks, lps
+
+    def _generate(self, prompts: list[list[int]], max_length: int | None, repetition_penalty: float,
+                  stats: GenerateStats | None, streams: list[int] | None,
+                  k: int = 1) -> tuple[list[list[int]], list[list[float]]]:
+        """(tokens, log-probabilities) per prompt in the mode of the scope around it; a prompt that
+        only passes through, or a mode without log-probabilities, gives ``[]`` for the second.
+        ``k`` > 1 (``_generate_groups``: no pass-through prompt, at most ``max_batch`` completions): k
+        completions per prompt from one forked prefill, returned flat, prompt i's at [i * k, (i + 1) * k)."""
+        T = self.max_length if max_length is None else max_length
+        if T != self.max_length:
+            raise ValueError(f"engine built for max_length={self.max_length}, got {T}")
+        if k > 1:  # from here on a row per completion; only the prefill knows about groups
+            groups, prompts = prompts, [p for p in prompts for _ in range(k)]
         n = len(prompts)
         if n == 0:
             return [], []
@@ -1800,7 +1963,7 @@ class HipGPT2Engine:
         ev1 = torch.cuda.Event(enable_timing=True)
         ev2 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-        self._prefill(prompts, B, repetition_penalty, streams)
+        self._prefill(prompts if k == 1 else groups, B, repetition_penalty, streams, k)
         ev1.record()
         steps_max = T - min(len(p) for p in prompts) - 1
         if steps_max > 0 and self._df_ok(B) and self._df_run(B, steps_max, repetition_penalty):
@@ -1951,13 +2114,27 @@ class TorchGPT2Engine:
     @torch.no_grad()
     def generate(self, prompts: list[list[int]], max_length: int | None = None, repetition_penalty: float = 1.2,
                  stats: GenerateStats | None = None, sampling: SamplingParams | None = None,
-                 controls: GenerationControls | None = None, logprobs: bool = False):
+                 controls: GenerationControls | None = None, logprobs: bool = False, n: int = 1):
         """``sampling``: tokens drawn by ``models.gpt2.reference_sample`` under ``sampling.seed``,
         prompt i on stream i (the HIP engine's rule).  ``controls``: the bans and stops of
         ``models.gpt2.banned_tokens`` / ``stop_hit``.  ``logprobs``: returns ``(tokens, logprobs)``,
-        the second from ``models.gpt2.teacher_forced_logprobs`` on the generated sequences."""
+        the second from ``models.gpt2.teacher_forced_logprobs`` on the generated sequences.
+        ``n`` > 1 (needs ``sampling``): the definition of n completions per prompt -- every prompt
+        repeated n times, so completion j of prompt i runs on stream ``i * n + j``, regrouped per prompt."""
         from ..models.gpt2 import reference_generate, teacher_forced_logprobs
 
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n: a positive integer, got {n!r}")
+        if n > 1:
+            if sampling is None:
+                raise ValueError("n > 1 needs sampling=: greedy completions of one prompt are all equal")
+            flat = self.generate([p for p in prompts for _ in range(n)], max_length, repetition_penalty, stats,
+                                 sampling, controls, logprobs)
+
+            def group(rows):
+                return [rows[i: i + n] for i in range(0, len(rows), n)]
+
+            return (group(flat[0]), group(flat[1])) if logprobs else group(flat)
         if logprobs:
             norm = passthrough(prompts, self.max_length if max_length is None else max_length,
                                self.cfg.eos_token_id)[2]

@@ -22,7 +22,9 @@ Engine protocol (``HipGPT2Engine`` implements it; tests use a CPU fake):
     decode(B, steps, repetition_penalty)        ``steps`` decode steps over slots [0, B)
                                                 (both with ``sampling=`` when the batcher samples and
                                                 ``controls=`` when it has generation controls,
-                                                ``logprobs=True`` when it returns log-probabilities)
+                                                ``logprobs=True`` when it returns log-probabilities;
+                                                ``admit`` alone with ``n=n`` when the batcher serves
+                                                n > 1 completions per request: n slots per prompt)
     finished_flags(B) -> list[int]              per-slot stop flags
     collect(slots) -> list[list[int]]           prompt + generated tokens (``logprobs=True``, only
                                                 then passed: ``(tokens, logprobs)``)
@@ -31,6 +33,7 @@ Engine protocol (``HipGPT2Engine`` implements it; tests use a CPU fake):
 from __future__ import annotations
 
 import heapq
+import math
 import os
 import threading
 import time
@@ -84,6 +87,7 @@ class _Req:
     t_submit: float = field(default_factory=time.perf_counter)
     t_first: float = 0.0
     steps_left: int = 0  # decode steps until max_length (an upper bound: EOS may come first)
+    slots: tuple = ()  # the KV slots it holds once admitted: one, or its n completions' (parent first)
 
 
 class Overloaded(RuntimeError):
@@ -92,10 +96,62 @@ class Overloaded(RuntimeError):
     microseconds instead of queueing queries until their client deadlines expire)."""
 
 
+SELECTORS = ("mean_logprob",)
+
+
+def pick_best(logprob_lists) -> int:
+    """Best of n by mean log-probability: the index of the list with the largest arithmetic mean.
+    The lists are judged as the engine returned them, EOS and stop tokens included.  Ties go to the
+    lowest index.  An empty list (nothing was generated) ranks below every non-empty list that can
+    be judged; a list with a NaN in it cannot be judged and ranks below every list without one, the
+    empty ones included."""
+    best, best_key = 0, None
+    for i, lp in enumerate(logprob_lists):
+        lp = [float(v) for v in lp]
+        if any(math.isnan(v) for v in lp):
+            key = (0, 0.0)
+        elif not lp:
+            key = (1, 0.0)
+        else:
+            key = (2, math.fsum(lp) / len(lp))
+        if best_key is None or key > best_key:
+            best, best_key = i, key
+    if best_key is None:
+        raise ValueError("pick_best: no candidates")
+    return best
+
+
+class GainMeter:
+    """What best of n bought: the running mean, over the answered requests, of the chosen
+    completion's mean log-probability minus the average of the means over its group (the lists
+    that can be judged: non-empty, no NaN).  A request whose chosen list cannot be judged is not
+    counted."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self.answers = 0
+        self._sum = 0.0
+
+    def add(self, logprob_lists, chosen: int):
+        means = [math.fsum(lp) / len(lp) if len(lp) and not any(math.isnan(v) for v in lp) else None
+                 for lp in logprob_lists]
+        if means[chosen] is None:
+            return
+        judged = [m for m in means if m is not None]
+        with self._lock:
+            self.answers += 1
+            self._sum += means[chosen] - math.fsum(judged) / len(judged)
+
+    @property
+    def mean(self) -> float | None:
+        with self._lock:
+            return self._sum / self.answers if self.answers else None
+
+
 class ContinuousBatcher:
     def __init__(self, engine, repetition_penalty: float = 1.2, chunk: int = 8, max_admit: int | None = None,
                  name: str = "tutor", stream_priority: int | None = None, max_queue: int = 0, sampling=None,
-                 controls=None, logprobs: bool = False):
+                 controls=None, logprobs: bool = False, n: int = 1, select: str | None = None):
         """``max_queue``: queries allowed to wait for a free KV slot before ``submit`` raises
         ``Overloaded`` (0 = unbounded; the tutoring servers default to one batch of slots).
         ``sampling`` (a ``SamplingParams``): tokens are drawn instead of greedy; it is forwarded to
@@ -104,7 +160,28 @@ class ContinuousBatcher:
         length and stop sequences, forwarded the same way as ``controls=`` (results keep their stop
         tokens, as they keep EOS).  ``logprobs``: every future resolves to ``(tokens, logprobs)``,
         one float per generated token; forwarded as ``logprobs=True`` the same way, to ``collect`` /
-        ``collect_async`` too."""
+        ``collect_async`` too.
+        ``n`` > 1: n completions per request from one prefill.  A request takes n slots at admission
+        (it waits, at the head of the queue, until n are free; the engine's ``admit`` gets ``n=n`` --
+        only then, so engines without the argument are called exactly as before) and retires as a
+        group: when all n slots are flagged finished they are collected in one ``collect_async`` and
+        freed together.  A sibling that finishes early idles as an inert row until then; freeing it
+        early is not done.  ``{name}_tokens`` counts every completion's tokens, ``{name}_request_ms``
+        requests.  ``select=None``: the future resolves to the list of the n results (each ``tokens`` or
+        ``(tokens, logprobs)``); ``select="mean_logprob"`` (needs ``logprobs=True``): to the one result
+        ``pick_best`` chooses."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n: a positive integer, got {n!r}")
+        if n > engine.max_batch:
+            raise ValueError(f"n = {n} completions per request do not fit the engine's {engine.max_batch} slots")
+        if select is not None and select not in SELECTORS:
+            raise ValueError(f"select: None or one of {SELECTORS}, got {select!r}")
+        if select is not None and not logprobs:
+            raise ValueError(f"select={select!r} needs logprobs=True")
+        self.n = n
+        self.select = select
+        self._admit_n = {"n": n} if n > 1 else {}
+        self.gain = GainMeter()  # (select set: chosen mean log-probability over its group's average)
         self.engine = engine
         self.sampling = sampling
         self.controls = controls
@@ -156,7 +233,7 @@ class ContinuousBatcher:
         eos, T = self.engine.cfg.eos_token_id, self.engine.max_length
         p = list(prompt) if len(prompt) else [eos]
         if len(p) >= T:  # nothing to generate (generate() pass-through semantics)
-            fut.set_result((p, []) if self.logprobs else p)
+            fut.set_result(self._resolve([(p, []) if self.logprobs else p for _ in range(self.n)]))
             return fut
         with self._cv:
             if self._stop:
@@ -170,6 +247,15 @@ class ContinuousBatcher:
             self._queue.append(_Req(p, fut))
             self._cv.notify()
         return fut
+
+    def _resolve(self, items: list):
+        """What a future resolves to, from its request's n results."""
+        if self.select is not None:
+            lps = [lp for _, lp in items]
+            best = pick_best(lps)
+            self.gain.add(lps, best)
+            return items[best]
+        return items[0] if self.n == 1 else items
 
     @property
     def failed(self) -> BaseException | None:
@@ -188,6 +274,7 @@ class ContinuousBatcher:
 
     @property
     def active(self) -> int:
+        """Occupied KV slots (n per live request)."""
         return len(self._active)
 
     # ------------------------------------------------------------------ scheduler thread
@@ -236,23 +323,26 @@ class ContinuousBatcher:
                         if not r.future.done():
                             r.future.set_exception(RuntimeError("batcher stopped"))
                     return
-                admits: list[tuple[int, _Req]] = []
-                while self._queue and self._free and len(admits) < self.max_admit:
+                admits: list[tuple[int, _Req]] = []  # (first slot, request)
+                while self._queue and len(self._free) >= self.n and len(admits) < self.max_admit:
                     r = self._queue.popleft()
                     # RUNNING from here on: a caller's cancel() (a gRPC deadline, asyncio.wait_for
                     # timing out on a wrap_future) can no longer race the result; a request
                     # cancelled while it queued is dropped
                     if r.future.set_running_or_notify_cancel():
-                        admits.append((heapq.heappop(self._free), r))
+                        r.slots = tuple(heapq.heappop(self._free) for _ in range(self.n))
+                        admits.append((r.slots[0], r))
             if admits:
                 ta = time.perf_counter()
                 with roctx_range("prefill"):
-                    eng.admit([r.prompt for _, r in admits], [s for s, _ in admits], self.penalty, **self._mode)
+                    eng.admit([r.prompt for _, r in admits], [s for _, r in admits for s in r.slots], self.penalty,
+                              **self._mode, **self._admit_n)
                 TRACER.complete("tutor.admit", ta, cat="tutor", n=len(admits),
                                 tokens=sum(len(r.prompt) for _, r in admits))
                 t_first = time.perf_counter()  # prefill (first token included) is enqueued
-                for s, r in admits:
-                    self._active[s] = r
+                for _, r in admits:
+                    for s in r.slots:
+                        self._active[s] = r
                     r.t_first = t_first
                     r.steps_left = max(0, eng.max_length - len(r.prompt) - 1)  # prefill made token 1
                     METRICS.observe(f"{self.name}_queue_ms", (ta - r.t_submit) * 1e3)
@@ -273,8 +363,9 @@ class ContinuousBatcher:
                 # max_length gives less than `steps`): an aborted chunk refunds exactly that
                 taken = {}
                 for s, r in self._active.items():
-                    taken[s] = min(steps, r.steps_left)
-                    r.steps_left -= taken[s]
+                    if s == r.slots[0]:  # once per request, under its first slot
+                        taken[s] = min(steps, r.steps_left)
+                        r.steps_left -= taken[s]
                 with roctx_range("decode_chunk"):
                     eng.decode(B, steps, self.penalty, **self._mode)
                     cur = (flags_async(eng, B), dict(self._active), health_async(eng), dataflow_status_async(eng),
@@ -299,15 +390,18 @@ class ContinuousBatcher:
                     # requests their step budget back so later chunks are not cut short
                     METRICS.inc(f"{self.name}_dataflow_aborts")
                     for s, r in prev[1].items():
-                        if self._active.get(s) is r:
+                        if s == r.slots[0] and self._active.get(s) is r:
                             r.steps_left += prev[4].get(s, 0)
                 # by identity: a slot retired one chunk earlier may already hold a new request
-                done = [s for s, r in prev[1].items() if s < len(flags) and flags[s] and self._active.get(s) is r]
-                if done:
+                # (a request is done when every one of its slots is flagged)
+                reqs = [(s, r) for s, r in prev[1].items() if s == r.slots[0] and self._active.get(s) is r
+                        and all(t < len(flags) and flags[t] for t in r.slots)]
+                if reqs:
+                    done = [t for _, r in reqs for t in r.slots]
                     handle = collect_async(eng, done, **self._collect_mode)
                     with self._cv:
-                        reqs = [(s, self._active.pop(s)) for s in done]
                         for s in done:
+                            del self._active[s]
                             heapq.heappush(self._free, s)
                     retiring = (reqs, handle)
                     METRICS.set(f"{self.name}_active", len(self._active))
@@ -320,12 +414,15 @@ class ContinuousBatcher:
         if self.logprobs:
             outs, lps = outs
         now = time.perf_counter()
-        for i, ((s, r), out) in enumerate(zip(reqs, outs)):
+        n = self.n
+        for i, (s, r) in enumerate(reqs):
+            group = outs[i * n: (i + 1) * n]  # the request's n completions, in slot (= stream) order
             self.completed += 1
-            n_new = len(out) - len(r.prompt)
+            new = [len(out) - len(r.prompt) for out in group]
             METRICS.observe(f"{self.name}_request_ms", (now - r.t_submit) * 1e3)
-            if n_new > 1:  # time per output token after the first
-                METRICS.observe(f"{self.name}_tpot_ms", (now - r.t_first) * 1e3 / (n_new - 1))
-            METRICS.inc(f"{self.name}_tokens", n_new)
+            if max(new) > 1:  # time per output token after the first (of the longest completion)
+                METRICS.observe(f"{self.name}_tpot_ms", (now - r.t_first) * 1e3 / (max(new) - 1))
+            METRICS.inc(f"{self.name}_tokens", sum(new))
             if not r.future.done():
-                r.future.set_result(out if lps is None else (out, lps[i]))
+                r.future.set_result(self._resolve(group if lps is None else
+                                                  list(zip(group, lps[i * n: (i + 1) * n]))))

@@ -33,7 +33,8 @@ CHECK_SITES = {1: "embed token id", 2: "position id", 3: "decode_update slot_map
                9: "attention slot", 10: "BERT token id", 11: "seen_set token id", 12: "sampler slot_map",
                13: "sampled token id", 14: "prefix fill slot", 15: "prefix fill length",
                16: "attention prefix length", 17: "logit_bans slot_map", 18: "logit_bans sequence length",
-               19: "token_logprob slot_map", 20: "token_logprob sequence length", 21: "token_logprob token id"}
+               19: "token_logprob slot_map", 20: "token_logprob sequence length", 21: "token_logprob token id",
+               22: "kv_fork source slot", 23: "kv_fork destination slot", 24: "kv_fork length"}
 SOURCES = ["api.hip", "gemm.hip", "norm.hip", "attention.hip", "decode.hip", "encoder.hip", "xgmi.hip", "skinny.hip", "gemm_ps.hip",
            "dataflow.hip", "mid.hip", "sample.hip", "controls.hip", "logprob.hip"]
 ARCH = os.environ.get("DLMS_OFFLOAD_ARCH", "gfx950")
@@ -157,6 +158,7 @@ def _bind(L):
         "dlms_argmax_reduce": [P, I, ctypes.c_longlong, P, I, P],
         "dlms_seen_set": [P, P, I, P, I, I, P],
         "dlms_kv_prefix_fill": [P, P, P, P, I, I, I, I, I, I, I, P],
+        "dlms_kv_fork": [P, P, P, P, I, I, I, I, I, I, P],
         "dlms_bert_embed_ln": [P, P, P, P, P, P, P, P, P, I, I, F, I, I, P],
         "dlms_mean_pool": [P, P, P, P, I, I, P],
         "dlms_cosine": [P, P, P, I, I, I, F, P],
@@ -781,6 +783,61 @@ def kv_prefix_fill(kv: torch.Tensor, store: torch.Tensor, slots: torch.Tensor, p
         raise ValueError("kv_prefix_fill: one prefix length per listed slot (1 .. 65535 slots)")
     _check(lib().dlms_kv_prefix_fill(_p(kv), _p(store), _p(slots), _p(pfx), n, 2 * L, S, H, T, store.shape[3],
                                      64 * kv.element_size(), _stream()), "dlms_kv_prefix_fill")
+    return kv
+
+
+def check_fork_pairs(src, dst, lens, n_slots: int):
+    """Host-side rules of a ``kv_fork`` table (sequences of ints): equal lengths, slots in
+    [0, n_slots), no slot written twice, and no slot both read and written by different pairs (a
+    read/write race between workgroups; ``src[i] == dst[i]`` is a no-op and allowed)."""
+    src, dst, lens = ([int(v) for v in a] for a in (src, dst, lens))
+    if not (len(src) == len(dst) == len(lens)):
+        raise ValueError(f"kv_fork: src, dst and lens differ in length ({len(src)}, {len(dst)}, {len(lens)})")
+    if not src:
+        raise ValueError("kv_fork: no pairs")
+    if min(src) < 0 or max(src) >= n_slots or min(dst) < 0 or max(dst) >= n_slots:
+        raise ValueError(f"kv_fork: slots must be in [0, {n_slots})")
+    if min(lens) < 0:
+        raise ValueError("kv_fork: negative length")
+    if len(set(dst)) != len(dst):
+        raise ValueError("kv_fork: a destination slot is listed twice")
+    written = {d for s, d in zip(src, dst) if s != d}
+    read = {s for s, d in zip(src, dst) if s != d}
+    both = written & read
+    if both:
+        raise ValueError(f"kv_fork: slot(s) {sorted(both)} are both read and written")
+
+
+def kv_fork(kv: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, lens: torch.Tensor, host_checked: bool = False):
+    """Best of n: for every pair i copy ``kv[l, kv, src[i], h, :lens[i]]`` to ``kv[l, kv, dst[i], h, :lens[i]]``
+    for every layer, K and V, and head -- one launch.  ``kv``: the whole cache [L, 2, slots, H, T, 64],
+    bf16 or the fp8 byte cache, contiguous; ``src`` / ``dst`` / ``lens``: int32 device arrays (read by
+    the kernel, so the call can be captured).  ``lens[i] = 0`` and ``src[i] == dst[i]`` copy nothing;
+    lengths are clamped to T.  The pairs must satisfy ``check_fork_pairs``; the wrapper reads the arrays
+    back to check them unless the caller built them on the host and did (``host_checked=True``: what a
+    captured call needs, since the read-back synchronises)."""
+    if not isinstance(kv, torch.Tensor):
+        raise TypeError("kv_fork: kv must be a tensor")
+    if kv.dtype not in (torch.bfloat16, FP8):
+        raise ValueError(f"kv_fork: kv is {kv.dtype}: bf16 or fp8")
+    _req(kv, kv.dtype, "kv", 6)
+    _req(src, torch.int32, "src", 1)
+    _req(dst, torch.int32, "dst", 1)
+    _req(lens, torch.int32, "lens", 1)
+    L, two, S, H, T, hd = kv.shape
+    if two != 2 or hd != 64:
+        raise ValueError("kv_fork: kv [L, 2, slots, H, T, 64]")
+    if not kv.is_contiguous() or kv.data_ptr() % 16:
+        raise ValueError("kv_fork: kv must be contiguous and 16-byte aligned")
+    n = src.numel()
+    if dst.numel() != n or lens.numel() != n:
+        raise ValueError(f"kv_fork: src, dst and lens differ in length ({n}, {dst.numel()}, {lens.numel()})")
+    if n == 0 or n > 65535 or not (src.is_contiguous() and dst.is_contiguous() and lens.is_contiguous()):
+        raise ValueError("kv_fork: 1 .. 65535 pairs in contiguous arrays")
+    if not host_checked:
+        check_fork_pairs(src.cpu().tolist(), dst.cpu().tolist(), lens.cpu().tolist(), S)
+    _check(lib().dlms_kv_fork(_p(kv), _p(src), _p(dst), _p(lens), n, 2 * L, S, H, T, 64 * kv.element_size(),
+                              _stream()), "dlms_kv_fork")
     return kv
 
 

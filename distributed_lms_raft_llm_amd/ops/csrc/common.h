@@ -307,7 +307,7 @@ enum {
     CHK_SEEN_ROW = 6, CHK_QKV_SLOT = 7, CHK_QKV_POS = 8, CHK_ATTN_SLOT = 9, CHK_BERT_TOKEN = 10,
     CHK_SEEN_TOKEN = 11, CHK_SAMPLE_SLOT = 12, CHK_SAMPLE_TOKEN = 13, CHK_PFX_SLOT = 14, CHK_PFX_LEN = 15,
     CHK_ATTN_PFX = 16, CHK_BANS_SLOT = 17, CHK_BANS_LEN = 18, CHK_LOGPROB_SLOT = 19, CHK_LOGPROB_LEN = 20,
-    CHK_LOGPROB_TOKEN = 21,
+    CHK_LOGPROB_TOKEN = 21, CHK_FORK_SRC = 22, CHK_FORK_DST = 23, CHK_FORK_LEN = 24,
 };
 
 struct DlmsCheckRecord {

@@ -372,4 +372,60 @@ extern "C" hipError_t dlms_kv_prefix_fill(void* kv, const void* store, const int
     return hipGetLastError();
 }
 
+// Best of n: fork freshly prefilled slots into sibling slots.  For every pair i the first lens[i] key
+// rows of slot src[i] go to slot dst[i], for every layer, K and V, and head: per (pair, layer, k/v,
+// head) one contiguous run of lens * row bytes on both sides of the cache [L][2][slots][H][t_max][row]
+// (row = 128 B bf16 or 64 B e4m3), moved as 16-byte chunks with plain loads and stores.  A unit is one
+// (pair, layer * 2 + k/v); a capped grid strides over the units (768 children x 24 units at the
+// serving shape: one workgroup per unit would be 18 k tiny workgroups), each workgroup looping over
+// its unit's heads' chunks.  src / dst / lens are read on the device (the staged fork table of a
+// captured prefill); lens = 0 and src == dst copy nothing, lengths are clamped to t_max, and a slot
+// outside the cache writes nothing.  The host guarantees that no slot is both read and written and
+// that no slot is written twice, so the workgroups never race; a parent may be read by many children.
+#define KV_FORK_MAX_GRID 2048
+__global__ __launch_bounds__(256) void kv_fork_kernel(unsigned char* __restrict__ kv, const int* __restrict__ src,
+                                                      const int* __restrict__ dst, const int* __restrict__ lens,
+                                                      int n, int layers2, int n_slots, int H, int t_max,
+                                                      int row_bytes) {
+    const int units = n * layers2;
+    const size_t head_bytes = (size_t)t_max * row_bytes;
+    for (int u = blockIdx.x; u < units; u += gridDim.x) {
+        const int i = u / layers2, lk = u - i * layers2;
+        const int s = src[i], d = dst[i];
+        if (s < 0 || s >= n_slots) {  // the host validates slots; never read or write outside the cache
+            dlms_idx(s, n_slots, CHK_FORK_SRC);
+            continue;
+        }
+        if (d < 0 || d >= n_slots) {
+            dlms_idx(d, n_slots, CHK_FORK_DST);
+            continue;
+        }
+        int p = (int)dlms_idx(lens[i], t_max + 1, CHK_FORK_LEN);
+        p = p < 0 ? 0 : (p > t_max ? t_max : p);  // never past the slot's rows
+        if (p == 0 || s == d) continue;
+        const int per_head = p * (row_bytes >> 4);  // 16-byte chunks of one head's run
+        const int total = H * per_head;
+        const unsigned char* from = kv + ((size_t)lk * n_slots + s) * H * head_bytes;
+        unsigned char* to = kv + ((size_t)lk * n_slots + d) * H * head_bytes;
+        for (int c = threadIdx.x; c < total; c += 256) {
+            const int h = c / per_head, rem = c - h * per_head;
+            const size_t off = (size_t)h * head_bytes + (size_t)rem * 16;
+            const uint4 v = *reinterpret_cast<const uint4*>(from + off);
+            *reinterpret_cast<uint4*>(to + off) = v;
+        }
+    }
+}
+
+extern "C" hipError_t dlms_kv_fork(void* kv, const int* src, const int* dst, const int* lens, int n, int layers2,
+                                   int n_slots, int H, int t_max, int row_bytes, hipStream_t stream) {
+    if (n <= 0 || layers2 <= 0 || n_slots <= 0 || H <= 0 || t_max <= 0 || n > 65535 || layers2 > 4096 ||
+        (row_bytes != 64 && row_bytes != 128) || (long long)H * t_max * (row_bytes >> 4) > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    const int units = n * layers2;  // < 2^28
+    hipLaunchKernelGGL(kv_fork_kernel, dim3(units < KV_FORK_MAX_GRID ? units : KV_FORK_MAX_GRID), dim3(256), 0,
+                       stream, reinterpret_cast<unsigned char*>(kv), src, dst, lens, n, layers2, n_slots, H, t_max,
+                       row_bytes);
+    return hipGetLastError();
+}
+
 DLMS_CHECK_EXPORT(decode)

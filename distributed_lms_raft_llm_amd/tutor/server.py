@@ -99,7 +99,15 @@ class _Req:
 class Batcher:
     """Dynamic batching in front of an engine with ``generate(prompts, max_length, penalty)``."""
 
-    def __init__(self, engine, gen: GenerationConfig, max_batch: int = 64, window_ms: float = 2.0):
+    def __init__(self, engine, gen: GenerationConfig, max_batch: int = 64, window_ms: float = 2.0, best_of: int = 1):
+        """``best_of`` > 1 (a sampling ``gen`` with ``logprobs``): every batch runs as
+        ``generate(..., n=best_of)`` and each query resolves to the completion ``pick_best`` chooses."""
+        from ..engine.scheduler import GainMeter
+
+        if best_of > 1 and not (gen.logprobs and gen.sampling() is not None):
+            raise ValueError("best_of > 1 needs a sampling GenerationConfig with logprobs")
+        self.best_of = best_of
+        self.gain = GainMeter()
         self.engine = engine
         self.gen = gen
         self.batches = 0  # sampling: batch i draws under seed + i (a run is reproducible, its batches differ)
@@ -141,6 +149,8 @@ class Batcher:
             mode = {} if ct is None else {"controls": ct}  # (only when set: engines are called as before)
             if self.gen.logprobs:
                 mode["logprobs"] = True
+            if self.best_of > 1:  # (only then: engines without the argument are called as before)
+                mode["n"] = self.best_of
             if sp is None:
                 outs = self.engine.generate([r.ids for r in batch], self.gen.max_length, self.gen.repetition_penalty,
                                             **mode)
@@ -158,7 +168,16 @@ class Batcher:
         if self.gen.logprobs:
             outs, lps = outs
         dt = time.perf_counter() - t0
-        new = sum(len(o) - len(r.ids) for o, r in zip(outs, batch))
+        if self.best_of > 1:  # one answer per query: the group's best; every completion's tokens are counted
+            from ..engine.scheduler import pick_best
+
+            new = sum(len(o) - len(r.ids) for g, r in zip(outs, batch) for o in g)
+            best = [pick_best(g) for g in lps]
+            for g, b in zip(lps, best):
+                self.gain.add(g, b)
+            outs, lps = [g[b] for g, b in zip(outs, best)], [g[b] for g, b in zip(lps, best)]
+        else:
+            new = sum(len(o) - len(r.ids) for o, r in zip(outs, batch))
         METRICS.observe("tutor_batch_size", len(batch))
         METRICS.observe("tutor_batch_ms", dt * 1e3)
         METRICS.inc("tutor_tokens_generated", new)
@@ -366,14 +385,19 @@ class TutoringServer:
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_batch: int = 64, window_ms: float = 2.0,
                  max_length: int = 150, repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None,
                  workers: int = 64, batching: str = "auto", chunk: int = 8, max_queue: int | None = None,
-                 sampling=None, controls=None, logprobs: bool = False, min_mean_logprob: float | None = None):
+                 sampling=None, controls=None, logprobs: bool = False, min_mean_logprob: float | None = None,
+                 best_of: int = 1):
         """``sampling`` (a ``SamplingParams``, every server class): answers are sampled, not greedy.
         ``controls`` (a ``GenerationControls``, every server class): n-gram blocking, a minimum length
         and stop sequences; a matched stop sequence is dropped from the answer.  ``logprobs`` (every
         server class): the engine returns the tokens' log-probabilities and the health record gains
         ``mean_token_logprob``; ``min_mean_logprob`` (implies it): also ``low_confidence_answers``.
-        The answers are unchanged."""
-        logprobs = bool(logprobs) or min_mean_logprob is not None
+        The answers are unchanged.  ``best_of`` > 1 (every server class; needs ``sampling``, implies
+        ``logprobs``): every query runs as ``best_of`` sampled completions of one prefill and is answered
+        with the one of the highest mean token log-probability (``engine/scheduler.py pick_best``); the
+        health record gains ``best_of`` and ``best_of_gain``, and the log-probability fields describe
+        the chosen answers."""
+        logprobs = self._init_best_of(best_of, sampling, logprobs, min_mean_logprob)
         self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
@@ -386,9 +410,10 @@ class TutoringServer:
                 raise ValueError("continuous batching: engine max_length differs from the server's")
             self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                              max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                             **_controls_kw(controls), **_logprobs_kw(logprobs))
+                                             **_controls_kw(controls), **_logprobs_kw(logprobs),
+                                             **_best_of_kw(best_of))
         else:
-            self.batcher = Batcher(engine, self.gen, max_batch=max_batch, window_ms=window_ms)
+            self.batcher = Batcher(engine, self.gen, max_batch=max_batch, window_ms=window_ms, best_of=best_of)
         self.batching = batching
         self.server = grpc.server(futures.ThreadPoolExecutor(max_workers=workers),
                                   options=[("grpc.max_send_message_length", wire.DEFAULT_MAX_MESSAGE),
@@ -401,6 +426,15 @@ class TutoringServer:
         self.port = self.server.add_insecure_port(f"{host}:{port}")
         if self.port == 0:
             raise RuntimeError(f"could not bind {host}:{port}")
+
+    def _init_best_of(self, best_of: int, sampling, logprobs, min_mean_logprob) -> bool:
+        """Check and keep ``best_of``; returns whether the engine is to return log-probabilities."""
+        if isinstance(best_of, bool) or not isinstance(best_of, int) or best_of < 1:
+            raise ValueError(f"best_of: a positive integer, got {best_of!r}")
+        if best_of > 1 and sampling is None:
+            raise ValueError("best_of > 1 needs sampling: greedy completions of one prompt are all equal")
+        self.best_of = best_of
+        return bool(logprobs) or min_mean_logprob is not None or best_of > 1
 
     def _health(self) -> dict:
         b = self.batcher
@@ -422,6 +456,8 @@ class TutoringServer:
             out.update(stopped_by_sequence=self.front.stopped_by_sequence)
         if isinstance(self.front, LogprobMeter):
             out.update(logprob_stats(self.front))
+        if getattr(self, "best_of", 1) > 1:
+            out.update(best_of_stats(self))
         if self.batching == "continuous":
             out.update(active=b.active, completed=b.completed, ok=b._error is None and b._thread.is_alive())
         else:
@@ -495,7 +531,7 @@ class AioTutoringServer(TutoringServer):
     def __init__(self, engine, port: int = 50054, host: str = "[::]", max_length: int = 150,
                  repetition_penalty: float = 1.2, tokenizer: GPT2BPE | None = None, chunk: int = 8,
                  max_queue: int | None = None, sampling=None, controls=None, logprobs: bool = False,
-                 min_mean_logprob: float | None = None):
+                 min_mean_logprob: float | None = None, best_of: int = 1):
         import asyncio
 
         from ..engine.scheduler import ContinuousBatcher
@@ -504,13 +540,13 @@ class AioTutoringServer(TutoringServer):
             raise ValueError("the aio front end needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        logprobs = bool(logprobs) or min_mean_logprob is not None
+        logprobs = self._init_best_of(best_of, sampling, logprobs, min_mean_logprob)
         self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.tok = tokenizer or GPT2BPE(eos_token_id=getattr(getattr(engine, "cfg", None), "eos_token_id", 50256))
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                          max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                         **_controls_kw(controls), **_logprobs_kw(logprobs))
+                                         **_controls_kw(controls), **_logprobs_kw(logprobs), **_best_of_kw(best_of))
         self.front = front_batcher(self.batcher, controls, logprobs, min_mean_logprob)
         self.batching = "continuous"
         self.engine = engine
@@ -559,19 +595,19 @@ class PooledTutoringServer(TutoringServer):
 
     def __init__(self, engine, pool, max_length: int = 150, repetition_penalty: float = 1.2, chunk: int = 8,
                  max_queue: int | None = None, sampling=None, controls=None, logprobs: bool = False,
-                 min_mean_logprob: float | None = None):
+                 min_mean_logprob: float | None = None, best_of: int = 1):
         from ..engine.scheduler import ContinuousBatcher
 
         if not hasattr(engine, "admit"):
             raise ValueError("the front-end pool needs a slot engine (continuous batching)")
         if engine.max_length != max_length:
             raise ValueError("continuous batching: engine max_length differs from the server's")
-        logprobs = bool(logprobs) or min_mean_logprob is not None
+        logprobs = self._init_best_of(best_of, sampling, logprobs, min_mean_logprob)
         self.gen = generation_config(max_length, repetition_penalty, sampling, controls, logprobs)
         self.controls = controls
         self.batcher = ContinuousBatcher(engine, repetition_penalty, chunk=chunk,
                                          max_queue=default_max_queue(engine, max_queue), sampling=sampling,
-                                         **_controls_kw(controls), **_logprobs_kw(logprobs))
+                                         **_controls_kw(controls), **_logprobs_kw(logprobs), **_best_of_kw(best_of))
         self.front = front_batcher(self.batcher, controls, logprobs, min_mean_logprob)
         self.batching = "continuous"
         self.engine = engine
@@ -618,6 +654,30 @@ def _controls_kw(controls) -> dict:
 
 def _logprobs_kw(logprobs) -> dict:
     return {"logprobs": True} if logprobs else {}
+
+
+def _best_of_kw(best_of: int) -> dict:
+    return {"n": best_of, "select": "mean_logprob"} if best_of > 1 else {}
+
+
+def best_of_stats(srv) -> dict:
+    """The health record's (and the exit line's) best-of-n fields: N, and the running mean over the
+    answered queries of the chosen answer's mean log-probability minus its group's average."""
+    g = srv.batcher.gain.mean
+    return {"best_of": srv.best_of, "best_of_gain": None if g is None else round(g, 4)}
+
+
+def apply_best_of(args) -> None:
+    """``--best-of N`` with N > 1 implies ``--sample`` and ``--logprobs`` (set on ``args``);
+    ``ValueError`` for N < 1 or an explicit ``--max-batch`` smaller than N."""
+    if args.best_of < 1:
+        raise ValueError("--best-of: a positive integer")
+    if args.best_of > 1:
+        if args.max_batch and args.max_batch < args.best_of:
+            raise ValueError(f"--best-of {args.best_of}: needs {args.best_of} decode slots per query, "
+                             f"--max-batch is {args.max_batch}")
+        args.sample = True
+        args.logprobs = True
 
 
 def logprob_stats(meter: "LogprobMeter") -> dict:
@@ -737,6 +797,12 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--min-mean-logprob", type=float, default=None, metavar="X",
                     help="implies --logprobs: also count the answers whose mean token log-probability is below X "
                          "(low_confidence_answers)")
+    ap.add_argument("--best-of", type=int, default=1, metavar="N",
+                    help="implies --sample and --logprobs: run every query as N sampled completions of one prefill "
+                         "(the prompt's K/V are forked into N decode slots) and answer with the one of the highest "
+                         "mean token log-probability; one answer per query, the wire format is unchanged; the "
+                         "health record and the exit line gain best_of and best_of_gain; --min-mean-logprob judges "
+                         "the chosen answer; bf16 weights on one GPU per replica")
     return ap
 
 
@@ -744,6 +810,7 @@ def main(argv=None):
     ap = arg_parser()
     args, _ = parse_with_config(ap, argv)
     try:
+        apply_best_of(args)
         sampling = sampling_from_args(args)
     except ValueError as e:
         ap.error(str(e))
@@ -752,7 +819,7 @@ def main(argv=None):
     want_controls = bool(args.no_repeat_ngram_size or args.min_new_tokens or args.stop)
     logprobs = args.logprobs or args.min_mean_logprob is not None
     for wanted, option, unsupported in (
-            (sampling is not None, "--sample", engine_mode.sampling_unsupported),
+            (sampling is not None, "--best-of" if args.best_of > 1 else "--sample", engine_mode.sampling_unsupported),
             (args.kv_dtype == "fp8", "--kv-dtype fp8", engine_mode.kv_fp8_unsupported),
             (args.prefix_cache == "on", "--prefix-cache on", engine_mode.prefix_unsupported),
             (want_controls, "--no-repeat-ngram-size / --min-new-tokens / --stop", engine_mode.controls_unsupported),
@@ -770,7 +837,9 @@ def main(argv=None):
     mode = {} if sampling is None else {"sampling": sampling}
     mode.update(_controls_kw(controls))
     mode.update(_logprobs_kw(logprobs))
-    srv_mode = dict(mode, min_mean_logprob=args.min_mean_logprob) if logprobs else mode
+    srv_mode = dict(mode, min_mean_logprob=args.min_mean_logprob) if logprobs else dict(mode)
+    if args.best_of > 1:
+        srv_mode["best_of"] = args.best_of
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -824,6 +893,11 @@ def main(argv=None):
                           latency_path={"auto": None, "on": True, "off": False}[args.latency_path],
                           prefix_capacity=PREFIX_CAPACITY if args.prefix_cache == "on" else 0)
     args.max_batch = getattr(eng, "max_batch", 0) or args.max_batch or 64
+    if args.max_batch < args.best_of:  # (the slots planned from free HBM: engine/memory.py)
+        if hasattr(eng, "close"):
+            eng.close()
+        raise SystemExit(f"--best-of {args.best_of}: the engine has {args.max_batch} decode slots, "
+                         f"a query needs {args.best_of}")
     tok = GPT2BPE(args.vocab, args.merges, eos_token_id=eng.cfg.eos_token_id)
     if args.prefix_cache == "on":  # (ahead of the graph captures below)
         prefix = enable_prefix_cache(eng, tok)
@@ -872,6 +946,8 @@ def main(argv=None):
     if isinstance(getattr(srv, "front", None), LogprobMeter):
         log.info("log-probabilities: %s over %d answered queries",
                  ", ".join(f"{k} {v}" for k, v in logprob_stats(srv.front).items()), srv.front.answers)
+    if args.best_of > 1:
+        log.info("best of n: %s", ", ".join(f"{k} {v}" for k, v in best_of_stats(srv).items()))
     if proxy is not None:
         proxy.close()  # releases the followers, which close their engines (below, same order)
         eng = proxy.engine
